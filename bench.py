@@ -2,6 +2,25 @@
 """bench.py — GCUPS of the MI355X Game-of-Life engine (BASELINE.json's metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bit131072|byte32768] [-k K]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets the
+boards up, settles the clock, warms up, times the K steps, writes the board
+the timed steps left if --dump-outputs is given, and prints the result line.
+Everything else described below (the light-cone verification, the clock
+probe's batch, `aged_board`, `config4_1000gen`, the secondary configurations,
+the CPU baselines, the N>1 halo diagnostic, the box's rocminfo record) runs
+only under --full, where the --no-* switches still drop single legs; in a
+plain run those keys are null.
+
+--dump-outputs DIR writes what a caller of the timed path holds after its last
+timed step, the board at generation (W+K)·k, as float32 0/1 cells: the whole
+board in DIR/board.npy when it fits 32 MB, otherwise DIR/board_sample.npy, a
+fixed (seeded) set of 512×512 windows of every slab (the grid's corners among
+them) with their [row, col, height, width] in DIR/board_sample_windows.npy;
+DIR/live_cells.npy holds the live-cell count of the whole board.  The input
+is the seeded grid and the settle phase runs on the twin, so the same
+arguments give the same files from run to run.
 
 One step = one pass of the hot path over the grid: ONE fused launch of
 `k` generations (plus, for N>1, one k-row halo exchange).  The timed region is
@@ -28,7 +47,11 @@ against an independent CPU computation (numpy, bit-parallel 8-neighbour
 counter) started from a cone copied asynchronously just before the warm-up;
 for N>1 ranks one more window straddles every slab seam (its cone halves held
 by the two ranks, gathered over gloo): `verify` lists them, `verified` is
-their AND.
+their AND.  The host stepper's cost grows with the cube of the generations, so
+a run of more than VERIFY_MAX_GENS generations (warm-up included) is checked
+over the VERIFY_MAX_GENS generations that follow its timed steps instead: the
+cones are copied behind the timed steps and the board is stepped on;
+`verified_generations` says which board generations the windows cover.
 
 Clock discipline: an MI355X that idled runs this kernel at
 ≈1.97 GHz and needs ≈0.25 s of load to reach ≈2.38 GHz, and even 5 ms of idle
@@ -71,6 +94,7 @@ sys.path.insert(0, ROOT)
 if int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) < 24:
     os.environ["GPU_MAX_HW_QUEUES"] = "24"
 
+VERIFY_MAX_GENS = 1280   # the longest light cone life_cpu steps (seconds; the cost grows with the cube)
 PROBE_MAX_MS = 5000.0   # the clock probe ends by itself after this (a timed window takes < 0.2 s)
 HBM_PEAK = 8.0e12                   # B/s, MI355X spec (MI355X_MICROARCH.md)
 VALU_PEAK = 256 * 4 * 32 * 2.4e9    # lane-ops/s: 256 CU × 4 SIMD × 32 lanes/clk (wave64 in 2 clk) × 2.4 GHz
@@ -150,7 +174,19 @@ def parse():
     p.add_argument("--no-halo-diag", action="store_true",
                    help="N>1: skip the halo diagnostic (comm-stream device time per step, and the same steps "
                         "with the exchange skipped: the interior-only step time and efficiency_vs_no_halo)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: the verification, the clock probe, aged_board, "
+                        "config4_1000gen, the secondary configurations, the CPU baselines, the halo diagnostic "
+                        "(N>1) and the rocminfo record; the --no-* switches drop single legs of it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the board the last timed step left (float32 cells; a seeded sample of windows when "
+                        "it exceeds 32 MB) and its live-cell count as DIR/*.npy; reproducible from run to run while "
+                        "the clock settles on the twin board (not under --aged-board or when the twin does not fit)")
+    args = p.parse_args()
+    if not args.full:   # a plain run: the headline's own steps only
+        args.no_cpu_baseline = args.no_secondary = args.no_verify = args.no_clock = True
+        args.no_aged = args.no_config4 = args.no_halo_diag = True
+    return args
 
 
 # ---------------------------------------------------------------- verification
@@ -809,6 +845,59 @@ def timed_window(eng, steps, k, launch_events, gh, gens=None):
     return t, ms, n
 
 
+DUMP_WHOLE_CELLS = 8 << 20   # float32 cells in 32 MB: boards up to this size are dumped whole
+DUMP_WINDOWS, DUMP_WINDOW = 32, 512   # otherwise: this many windows of this edge (32 MB at most)
+
+
+def dump_windows(rows_per: int, n_slabs: int, cols: int) -> tuple[bool, list[tuple[int, int, int, int]]]:
+    """What --dump-outputs copies from the board, as (row, col, height, width)
+    pieces that each lie inside one row slab (a rank holds only its own): every
+    slab whole when the board fits DUMP_WHOLE_CELLS, else DUMP_WINDOWS windows
+    spread evenly over the slabs, the first four of a slab in its corners (the
+    grid's corners and the slab seams) and the rest at positions drawn from a
+    fixed seed.  Depends on the shape alone."""
+    if rows_per * n_slabs * cols <= DUMP_WHOLE_CELLS:
+        return True, [(j * rows_per, 0, rows_per, cols) for j in range(n_slabs)]
+    h, w = min(DUMP_WINDOW, rows_per), min(DUMP_WINDOW, cols)
+    rng = np.random.default_rng(20260)
+    out = []
+    for j in range(n_slabs):
+        n = DUMP_WINDOWS // n_slabs + (1 if j < DUMP_WINDOWS % n_slabs else 0)
+        spots = list(dict.fromkeys([(0, 0), (0, cols - w), (rows_per - h, 0), (rows_per - h, cols - w)]))
+        while len(spots) < n:   # (a board too large to dump whole has far more than n places for a window)
+            s = (int(rng.integers(0, rows_per - h + 1)), int(rng.integers(0, cols - w + 1)))
+            if s not in spots:
+                spots.append(s)
+        out += [(j * rows_per + r, c, h, w) for r, c in spots[:n]]
+    return False, out
+
+
+def dump_outputs(path, eng, rows_per, n_slabs, cols, live, dist, rank, world):
+    """--dump-outputs: copy the pieces of dump_windows from the board as it
+    stands (call it right after the timed steps), each rank those of its own
+    slab, and have rank 0 write them with the live-cell count (`live`: this
+    rank's, summed here)."""
+    whole, wins = dump_windows(rows_per, n_slabs, cols)
+    mine = [(i, eng.download_window(*win)) for i, win in enumerate(wins)
+            if world == 1 or win[0] // rows_per == rank]
+    parts, lives = [mine], [live]
+    if dist is not None:
+        parts, lives = [None] * world, [None] * world
+        dist.all_gather_object(parts, mine)
+        dist.all_gather_object(lives, live)
+    if rank != 0:
+        return
+    got = [a for _, a in sorted((p for ps in parts for p in ps), key=lambda p: p[0])]
+    assert len(got) == len(wins), (len(got), len(wins))
+    os.makedirs(path, exist_ok=True)
+    if whole:
+        np.save(os.path.join(path, "board.npy"), np.vstack(got).astype(np.float32))
+    else:
+        np.save(os.path.join(path, "board_sample.npy"), np.stack(got).astype(np.float32))
+        np.save(os.path.join(path, "board_sample_windows.npy"), np.array(wins, np.float64))
+    np.save(os.path.join(path, "live_cells.npy"), np.array([sum(lives)], np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -937,6 +1026,12 @@ def run(args, world, rank):
     # one process: across the first slab seam) and, for N>1 ranks, one across
     # every slab seam (SeamCheck)
     gens_v = (args.warmup + steps) * k
+    # life_cpu steps the whole cone, (64 + 2·gens)² cells for gens generations: 1 s at
+    # 1000 generations, hours at 10 000.  A longer run is checked over the VERIFY_MAX_GENS
+    # generations that follow its timed steps instead (cones taken behind the timed steps)
+    tail_v = gens_v > VERIFY_MAX_GENS
+    if tail_v:
+        gens_v = VERIFY_MAX_GENS // k * k
     cone = seams = None
     if not args.no_verify:
         lo, hi = (rank * rows_per, (rank + 1) * rows_per) if world > 1 else (0, rows)
@@ -971,9 +1066,14 @@ def run(args, world, rank):
         # two RCCL communicators must not run at once (their kernels can block
         # each other): the twin's settle steps drain before the headline board moves
         twin.sync()
-    verifier = Verifier(eng, **cone) if cone else None
-    if cone and world > 1:
-        seams = SeamCheck(eng, rank, world, rows_per, cols, seam_c0, gens_v, w=min(64, cols))
+    def take_cones():
+        v = Verifier(eng, **cone) if cone else None
+        s = None
+        if cone and world > 1:
+            s = SeamCheck(eng, rank, world, rows_per, cols, seam_c0, gens_v, w=min(64, cols))
+        return v, s
+
+    verifier, seams = (None, None) if tail_v else take_cones()
     eng.set_option(gh.OPT_KERNEL_TIMING, 1 if args.launch_events else 0)
     eng.step(args.warmup * k)
 
@@ -1004,6 +1104,11 @@ def run(args, world, rank):
     if not args.launch_events:   # one event pair around the whole timed batch (gol_sync): launches + gaps
         kernel_ms = dev_ms
     live = eng.popcount()
+    if args.dump_outputs:   # the board as the timed steps left it (before the clock batch steps it on)
+        dump_outputs(args.dump_outputs, eng, rows_per, n_total, cols, live, dist, rank, world)
+    if tail_v and cone:   # a long run: the checked generations are the next gens_v, on every rank
+        verifier, seams = take_cones()
+        eng.step(gens_v)
     if verifier:
         verifier.grab(eng)
     my_pieces = seams.pieces(eng) if seams is not None else None
@@ -1191,12 +1296,17 @@ def run(args, world, rank):
         "roofline": roofline,
         "verified": all_ok,
         "verify": verify,
+        # the board generations the windows cover: the warm-up and the timed steps, or (a run too
+        # long for the host stepper) the VERIFY_MAX_GENS generations that follow the timed steps
+        "verified_generations": ([(args.warmup + steps) * k, (args.warmup + steps) * k + gens_v] if tail_v
+                                 else [0, gens_v]) if verify else None,
         "board": ("the seeded grid (srand(1) row-major, main.cpp:68-77): the timed steps are its generations "
                   f"{args.warmup * k}..{(args.warmup + steps) * k}; the clock settled on a twin board"
                   if twin is not None else "aged by the settle phase (" + (
                       "--aged-board)" if args.aged_board else "a twin context's streams would exceed the "
                       "hardware queues)")),
-        "clock": clock if clock else {"skipped": "under rocprofv3" if profiled else "--no-clock"},
+        "clock": clock if clock else {"skipped": "a plain run (--full measures it)" if not args.full else
+                                      "under rocprofv3" if profiled else "--no-clock"},
         "aged_board": aged_line,
         "config4_1000gen": c4_line,
         "halo": halo,
@@ -1218,7 +1328,7 @@ def run(args, world, rank):
     elif rank == 0:
         result["cpu_baseline"] = None
     if rank == 0:
-        result["gpu"] = gpu_info()
+        result["gpu"] = gpu_info() if args.full else None
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -98,7 +98,7 @@ class _FakeEngine:
         pass
 
 
-def _rank(rank, world, port, q, corrupt=False, split=False):
+def _rank(rank, world, port, q, corrupt=False, split=False, argv=("--full",)):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     _FakeEngine.corrupt_halo = corrupt
@@ -109,7 +109,7 @@ def _rank(rank, world, port, q, corrupt=False, split=False):
     golhip.unique_id = lambda: bytes(range(128))
     mpi_amd.golhip = golhip
     import bench
-    sys.argv = ["bench.py", "--gpus", str(world), "--rows", "256", "--cols", "160", "-k", "2", "--steps", "3",
+    sys.argv = ["bench.py", *argv, "--gpus", str(world), "--rows", "256", "--cols", "160", "-k", "2", "--steps", "3",
                 "--warmup", "1", "--settle-s", "0.2", "--no-secondary"]
     out = io.StringIO()
     real = sys.stdout
@@ -122,11 +122,11 @@ def _rank(rank, world, port, q, corrupt=False, split=False):
     q.put((rank, out.getvalue(), e.steps))
 
 
-def _run_world2(corrupt=False, split=False):
+def _run_world2(corrupt=False, split=False, argv=("--full",)):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_rank, args=(r, 2, port, q, corrupt, split)) for r in range(2)]
+    procs = [ctx.Process(target=_rank, args=(r, 2, port, q, corrupt, split, argv)) for r in range(2)]
     for p in procs:
         p.start()
     res = dict((r, (o, s)) for r, o, s in (q.get(timeout=240) for _ in procs))
@@ -191,7 +191,7 @@ def test_bench_main_single_rank(monkeypatch, capsys):
     import bench
     for key in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         monkeypatch.delenv(key, raising=False)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--rows", "200", "--cols", "160", "-k", "2", "--steps", "3",
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--rows", "200", "--cols", "160", "-k", "2", "--steps", "3",
                                       "--warmup", "1", "--settle-s", "0.05", "--no-secondary", "--no-cpu-baseline"])
     _FakeEngine.instances.clear()
     bench.main()
@@ -287,7 +287,7 @@ def test_bench_clock_batch_after_timed_steps(monkeypatch, capsys):
     import bench
     for key in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         monkeypatch.delenv(key, raising=False)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--rows", "200", "--cols", "160", "-k", "2", "--steps", "3",
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--rows", "200", "--cols", "160", "-k", "2", "--steps", "3",
                                       "--warmup", "1", "--settle-s", "0.05", "--no-secondary", "--no-cpu-baseline"])
     _FakeEngine.instances.clear()
     bench.main()
@@ -310,7 +310,7 @@ def _rank_probe(rank, world, port, q):
     golhip.unique_id = lambda: bytes(range(128))
     mpi_amd.golhip = golhip
     import bench
-    sys.argv = ["bench.py", "--gpus", str(world), "--rows", "256", "--cols", "160", "-k", "2", "--steps", "3",
+    sys.argv = ["bench.py", "--full", "--gpus", str(world), "--rows", "256", "--cols", "160", "-k", "2", "--steps", "3",
                 "--warmup", "1", "--settle-s", "0.2", "--no-secondary"]
     out = io.StringIO()
     real = sys.stdout
@@ -340,3 +340,117 @@ def test_bench_world2_clock_batch():
     assert res[0][1] == res[1][1] == 3 * 2
     assert d["verified"] is True and any("seam" in v for v in d["verify"])
     assert d["clock"]["sclk_mhz"] == 2300.0
+
+
+class _CountingFakeEngine(_ProbeFakeEngine):
+    """The stand-in that counts the window copies taken from it."""
+
+    def download_window(self, r0, c0, h, w):
+        self.copies = getattr(self, "copies", 0) + 1
+        return super().download_window(r0, c0, h, w)
+
+
+def _plain_main(monkeypatch, capsys, extra=()):
+    sys.path.insert(0, ROOT)
+    import mpi_amd
+    from mpi_amd import golhip
+    monkeypatch.setattr(golhip, "Engine", _CountingFakeEngine)
+    monkeypatch.setattr(mpi_amd, "golhip", golhip)
+    import bench
+    for key in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(key, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--rows", "200", "--cols", "160", "-k", "2",
+                                      "--steps", "3", "--warmup", "1", "--settle-s", "0.05", *extra])
+    _FakeEngine.instances.clear()
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean(monkeypatch, capsys):
+    """Without --full the run is the headline alone: two boards (the seeded grid
+    and the twin the clock settles on), warm-up + timed steps on the first, no
+    window copied, no probe, and the legs beside the headline null in the line,
+    whose contract keys stay."""
+    d = _plain_main(monkeypatch, capsys)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert key in d, key
+    assert d["unit"] == "GCUPS" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 200 * 160 * 3 * 2 / (d["ms_per_step"] * 3 * 1e-3) / 1e9) < 1e-9 * d["value"]
+    assert d["verified"] is None and d["verify"] == [] and d["aged_board"] is None and d["config4_1000gen"] is None
+    assert d["cpu_baseline"] is None and d["gpu"] is None and d["halo"] is None and "secondary" not in d
+    assert "sclk_mhz" not in d["clock"] and "--full" in d["clock"]["skipped"]
+    assert len(_FakeEngine.instances) == 2
+    eng, twin = _FakeEngine.instances
+    assert eng.steps == (1 + 3) * 2 and not hasattr(eng, "probe_from") and not hasattr(twin, "probe_from")
+    assert getattr(eng, "copies", 0) == 0 and getattr(twin, "copies", 0) == 0
+    assert d["settle"]["on_second_board"] is True and twin.steps >= 25 * 2
+
+
+def test_bench_dump_outputs_whole_board(monkeypatch, capsys, tmp_path):
+    """--dump-outputs: the board the last timed step left, generation (W+K)·k of
+    the seeded grid whatever the settle phase did, as float32 cells, and its
+    live-cell count; the same under --full, where the clock batch steps the
+    board on after the copy."""
+    from oracle import golcpu as g
+    want = g.run(g.init_dead(200, 160, 1), (1 + 3) * 2, g.DEAD)
+    for extra in ((), ("--full", "--no-secondary", "--no-cpu-baseline")):
+        out = tmp_path / ("full" if extra else "plain") / "nested"
+        d = _plain_main(monkeypatch, capsys, ("--dump-outputs", str(out), *extra))
+        assert sorted(os.listdir(out)) == ["board.npy", "live_cells.npy"]
+        board, live = np.load(out / "board.npy"), np.load(out / "live_cells.npy")
+        assert board.dtype == np.float32 and board.shape == (200, 160) and (board == want).all()
+        assert live.dtype == np.float64 and live.tolist() == [float(want.sum())] and d["live_cells"] == want.sum()
+        assert (_FakeEngine.instances[0].steps > (1 + 3) * 2) == bool(extra)
+
+
+def test_bench_dump_windows_of_a_large_board():
+    """The headline's shape (and 8 slabs of it) is dumped as a fixed sample: the
+    same windows from call to call, each inside the grid and inside one slab,
+    the grid's four corners among them, 64 MB of float32 at the most."""
+    import bench
+    for rows_per, n, cols in ((131072, 1, 131072), (131072, 8, 131072), (4096, 3, 8192), (300, 1, 40000)):
+        whole, wins = bench.dump_windows(rows_per, n, cols)
+        assert not whole and (whole, wins) == bench.dump_windows(rows_per, n, cols)
+        assert len(wins) == len(set(wins)) == bench.DUMP_WINDOWS
+        assert sum(h * w for _, _, h, w in wins) * 4 <= 64 << 20
+        for r, c, h, w in wins:
+            assert h > 0 and w > 0 and 0 <= c and c + w <= cols
+            assert r // rows_per == (r + h - 1) // rows_per < n and r >= 0
+        assert sorted(r // rows_per for r, _, _, _ in wins) == sorted(i % n for i in range(len(wins)))
+        R, h, w = rows_per * n, wins[0][2], wins[0][3]
+        assert {(0, 0, h, w), (0, cols - w, h, w), (R - h, 0, h, w), (R - h, cols - w, h, w)} <= set(wins)
+    whole, wins = bench.dump_windows(1024, 2, 4096)
+    assert whole and wins == [(0, 0, 1024, 4096), (1024, 0, 1024, 4096)]
+
+
+def test_bench_dump_outputs_world2(tmp_path):
+    """Two ranks: each copies the rows of its own slab, rank 0 writes the board."""
+    from oracle import golcpu as g
+    d, _ = _run_world2(argv=("--dump-outputs", str(tmp_path)))
+    assert d["n_gpus"] == 2 and d["verified"] is None and d["halo"] is None
+    want = g.run(g.init_dead(512, 160, 1), (1 + 3) * 2, g.DEAD)
+    assert sorted(os.listdir(tmp_path)) == ["board.npy", "live_cells.npy"]
+    board = np.load(tmp_path / "board.npy")
+    assert board.dtype == np.float32 and (board == want).all()
+
+
+def test_bench_full_long_run_verifies_the_generations_after_the_timed_steps(monkeypatch, capsys):
+    """A --full run longer than bench.VERIFY_MAX_GENS (the host stepper's cost
+    grows with the cube of the generations): the timed steps run untouched, the
+    cone is copied behind them, the board is stepped VERIFY_MAX_GENS further and
+    the window checked there, before the clock batch; at the limit itself the
+    check covers the warm-up and the timed steps as ever."""
+    import bench
+    monkeypatch.setattr(bench, "VERIFY_MAX_GENS", 7)   # -> 6 generations at k = 2; the run has (1 + 3) * 2 = 8
+    d = _plain_main(monkeypatch, capsys, ("--full", "--no-secondary", "--no-cpu-baseline"))
+    eng = _FakeEngine.instances[0]
+    assert eng.steps == (1 + 3) * 2 + 6 + 3 * 2 and eng.probe_steps == 3 * 2
+    assert d["verified"] is True and d["verify"][0]["generations"] == 6 and d["verified_generations"] == [8, 14]
+    assert d["steps"] == 3 and d["roofline"]["launches"] == 3
+    monkeypatch.setattr(bench, "VERIFY_MAX_GENS", 8)
+    d = _plain_main(monkeypatch, capsys, ("--full", "--no-secondary", "--no-cpu-baseline"))
+    assert _FakeEngine.instances[0].steps == (1 + 3) * 2 + 3 * 2
+    assert d["verified"] is True and d["verify"][0]["generations"] == 8 and d["verified_generations"] == [0, 8]

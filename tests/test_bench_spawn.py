@@ -8,7 +8,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--gpus", "2", "--rows", "256", "--cols", "160", "-k", "2", "--steps", "3", "--warmup", "1",
+ARGS = ["--full", "--gpus", "2", "--rows", "256", "--cols", "160", "-k", "2", "--steps", "3", "--warmup", "1",
         "--settle-s", "0.2", "--no-secondary"]
 
 

@@ -4,10 +4,12 @@ unchanged").
 
 tests/golden/gol_sets/ holds small snapshot sets written by mpi_amd/bin/gol on
 an MI355X (serial mode with 1 and 2 parts, MPI mode P=4 on 2 parts, dead mode
-on 3 parts).  This CPU test runs /root/reference/gol_visualization.py BY PATH
-on each set (matplotlib Agg, pcolor/pause recorded instead of drawn) and checks
-that it loads every iteration and that the parts tile the whole board.  It is
-skipped where /root/reference is absent (the GPU box).  The cells themselves
+on 3 parts).  This CPU test runs the consumer BY PATH from oracle/_ref/, where
+`make -C oracle ref` (build()) stages it unmodified beside the reference
+binaries wherever the reference sources are present (never committed), on each
+set (matplotlib Agg, pcolor/pause recorded instead of drawn) and checks that
+it loads every iteration and that the parts tile the whole board.  It is
+skipped where build() found no reference sources.  The cells themselves
 are checked against the oracle from the same files (the consumer's own
 str->bool conversion makes every parsed cell True under numpy 2).
 """
@@ -23,7 +25,7 @@ from oracle import golcpu as g
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETS = os.path.join(ROOT, "tests", "golden", "gol_sets")
-CONSUMER = "/root/reference/gol_visualization.py"
+CONSUMER = os.path.join(ROOT, "oracle", "_ref", "gol_visualization.py")
 
 RUNNER = r"""
 import json, runpy, sys
@@ -48,7 +50,7 @@ def set_dirs():
     return sorted(glob.glob(os.path.join(SETS, "*")))
 
 
-@pytest.mark.skipif(not os.path.exists(CONSUMER), reason="the reference consumer is only in the build container")
+@pytest.mark.skipif(not os.path.exists(CONSUMER), reason="build() staged no reference consumer (no reference sources here)")
 @pytest.mark.parametrize("d", set_dirs(), ids=os.path.basename)
 def test_reference_consumer_reads_driver_output(d):
     mf = main_file(d)

@@ -32,6 +32,36 @@ def test_bench_json_line(workload):
     assert d["live_cells"] > 0
 
 
+@pytest.mark.parametrize("workload,rows,cols", [("bit131072", 2048, 4096), ("byte32768", 1000, 4100)])
+def test_bench_plain_run_dumps_the_timed_board(workload, rows, cols, tmp_path):
+    """A plain run (no --full) with --dump-outputs: the line is the headline
+    alone, and DIR/board.npy is what the timed steps left, generation (W+K)·k
+    of the seeded grid bit for bit (the settle steps ran on the twin), with
+    its live-cell count.  bit: 8 Mi cells, the largest board dumped whole;
+    byte: odd sizes, two strips."""
+    import numpy as np
+
+    from oracle import golcpu as g
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", workload,
+                        "--rows", str(rows), "--cols", str(cols), "--steps", "2", "--warmup", "1", "--settle-s", "0.2",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["value"] - rows * cols * d["config"]["generations"] / (2 * d["ms_per_step"] * 1e-3) / 1e9) \
+        < 1e-9 * d["value"]
+    assert d["verified"] is None and d["aged_board"] is None and d["config4_1000gen"] is None
+    assert d["cpu_baseline"] is None and "secondary" not in d and "skipped" in d["clock"]
+    k = d["config"]["gens_per_step"]
+    want = g.run_dead_fast(g.init_dead(rows, cols, 1), (1 + 2) * k)
+    assert sorted(os.listdir(tmp_path / "out")) == ["board.npy", "live_cells.npy"]
+    board = np.load(tmp_path / "out" / "board.npy")
+    assert board.dtype == np.float32 and board.shape == (rows, cols) and (board == want).all()
+    assert np.load(tmp_path / "out" / "live_cells.npy").tolist() == [float(want.sum())] and d["live_cells"] == want.sum()
+
+
 @pytest.mark.timeout(300)
 def test_bench_config4_valu_roofline():
     """The roofline branch the driver's line takes: config 4's
@@ -42,7 +72,7 @@ def test_bench_config4_valu_roofline():
     B/cell × 131072² per step ÷ the same time ÷ 8 TB/s.  Under the split
     interior (the default) the unit is the step (two half-launches + the seam
     band) and the record is traffic.json's per-step bit131072_k16_split."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2",
                         "--no-cpu-baseline", "--no-secondary", "--no-aged", "--no-config4", "--settle-s", "0.2"],
                        capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -79,7 +109,7 @@ def test_bench_single_process_eight_slabs():
     context's 16 more streams would exceed the 24 hardware queues and share
     queues with the headline's (92-107 k instead of 141-145 k)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--single-process", "--gpus", "8", "--steps",
-                        "3", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--settle-s", "0.2"],
+                        "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary", "--settle-s", "0.2"],
                        capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
@@ -96,7 +126,7 @@ def test_bench_two_ranks_real_rccl_same_device():
     per rank, RCCL's socket transport).  The rate is no scaling number; the
     line must be verified across the seam."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--steps", "4",
-                        "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--settle-s", "0.2"],
+                        "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary", "--settle-s", "0.2"],
                        capture_output=True, text=True, timeout=380)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])

@@ -8,7 +8,7 @@ mkdir -p "$(dirname "$OUT")"
 for r in $(seq 1 "$ROUNDS"); do
   for v in "$@"; do
     if [ "$v" = base ]; then L=mpi_amd/libgolhip.so; else L=mpi_amd/libgolhip_$v.so; fi
-    GOL_LIB=$L timeout -k 10 300 python bench.py $ARGS --no-secondary --no-cpu-baseline 2>/dev/null > /tmp/bench_ab_line.json
+    GOL_LIB=$L timeout -k 10 300 python bench.py --full $ARGS --no-secondary --no-cpu-baseline 2>/dev/null > /tmp/bench_ab_line.json
     python3 - "$v" "$r" >> "$OUT" <<'PY'
 import json, sys
 d = json.load(open("/tmp/bench_ab_line.json"))

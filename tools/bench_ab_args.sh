@@ -8,7 +8,7 @@ OUT=$1; ROUNDS=$2; ARGS=$3; shift 3
 mkdir -p "$(dirname "$OUT")"
 for r in $(seq 1 "$ROUNDS"); do
   for v in "$@"; do
-    timeout -k 10 300 python bench.py $ARGS $v --no-secondary --no-cpu-baseline 2>/dev/null > /tmp/bench_ab_line.json
+    timeout -k 10 300 python bench.py --full $ARGS $v --no-secondary --no-cpu-baseline 2>/dev/null > /tmp/bench_ab_line.json
     python3 - "$v" "$r" >> "$OUT" <<'PY'
 import json, sys
 d = json.load(open("/tmp/bench_ab_line.json"))

@@ -16,7 +16,7 @@ ARGS=("$@")
 run() {   # name, rocprof args...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 "$@" --output-format csv -d "$OUT/prof_${TAG}_${name}" -o run -- \
-    python3 "$REPO/bench.py" "${ARGS[@]}" --no-clock > "$OUT/prof_${TAG}_${name}.json" 2> "$OUT/prof_${TAG}_${name}.err"
+    python3 "$REPO/bench.py" --full "${ARGS[@]}" --no-clock > "$OUT/prof_${TAG}_${name}.json" 2> "$OUT/prof_${TAG}_${name}.err"
 }
 run kt --kernel-trace --stats
 run fetch --pmc FETCH_SIZE
