@@ -49,6 +49,13 @@ extern "C" {
 #define GOL_MESH_COMPAT 2   /* main.cpp on a √P×√P mesh, P=mesh_m²: swapped column halos
                                (main.cpp:51-54); any layout and tblock_k (stored as a dead-boundary
                                board with its column blocks in reverse order) */
+#define GOL_TORUS 3         /* periodic B3/S23 (the other value of main.cpp:243's periods): row -1 is
+                               row rows-1, column -1 is column cols-1.  Any layout, tblock_k = K and
+                               slab count with cols >= K and every slab (a single one too) >= K
+                               rows; mesh_m is ignored.  Stored with K ghost columns per side that a
+                               wrap kernel refreshes after every launch, and the halo exchange closed
+                               into a ring; gol_init_glibc: GOL_INIT_STREAM only (the cells of a
+                               GOL_DEAD board of that size and seed) */
 
 /* Seeded initialisation (glibc rand()%3==0, main.cpp:73 / main_serial.cpp:40) */
 #define GOL_INIT_STREAM 0 /* srand(seed), row-major over the global grid (MPI np=1 with seed 0≡1) */

@@ -10,11 +10,14 @@
 // compute goes through the C ABI of include/golhip.h.
 //
 // Options
-//   --mode mpi|serial|dead  mpi (default): main.cpp semantics on a √P×√P mesh of
+//   --mode mpi|serial|dead|torus
+//                           mpi (default): main.cpp semantics on a √P×√P mesh of
 //                           --procs P emulated ranks (P=1: dead boundary);
 //                           serial: main_serial.cpp semantics (writes gen 0 and
 //                           every gap, like the serial program);
-//                           dead: textbook non-periodic B3/S23, any rows×cols.
+//                           dead: textbook non-periodic B3/S23, any rows×cols;
+//                           torus: periodic B3/S23 (GOL_TORUS), the cells of dead's
+//                           generation 0; rows / gpus and cols at least K.
 //   --procs P               emulated MPI ranks for --mode mpi (default 1)
 //   --gpus N                row slabs / GPUs (default 1)
 //   --layout bit|byte       cell layout (default: bit; byte when --procs P has
@@ -230,8 +233,11 @@ int main(int argc, char **argv) {
         save = o.save != 0;
     } else if (o.mode == "dead") {
         save = o.save == 1;
+    } else if (o.mode == "torus") {
+        boundary = GOL_TORUS;
+        save = o.save == 1;
     } else {
-        die("--mode must be mpi, serial or dead");
+        die("--mode must be mpi, serial, dead or torus");
     }
     if (o.seed >= 0) seed = (uint32_t)o.seed;
     if (gap <= 0 && save) die("iteration_gap must be positive when saving");

@@ -23,6 +23,44 @@ __host__ __device__ inline int bit_pos(int64_t c, int gw) {
     return (int)((c & (32 * gw - 1)) >> lg);
 }
 
+// n <= 32 consecutive columns [c0, c0+n) of one bit-layout row as a u32 (bit i =
+// column c0+i), and back (only those columns' bits change).  A group holds at
+// least 64 columns, so the range touches at most two groups, and in each word
+// the wanted columns are one contiguous bit field [lo, hi): bit b of word j of
+// group g is column 32gw·g + gw·b + j.  (GOL_TORUS ghost margins: launch_wrap_cols.)
+template <typename F>
+__host__ __device__ inline void for_col_fields(int64_t c0, int n, int gw, F &&fn) {
+    const int lg = gw == 4 ? 2 : 1;
+    const int64_t gc = 32 * gw;
+    for (int64_t g = c0 / gc; g <= (c0 + n - 1) / gc; ++g)
+        for (int j = 0; j < gw; ++j) {
+            const int64_t base = g * gc + j;   // the column of this word's bit 0
+            const int64_t a = c0 - base, e = c0 + n - base;
+            const int lo = a <= 0 ? 0 : (int)((a + gw - 1) >> lg);
+            int hi = e <= 0 ? 0 : (int)((e + gw - 1) >> lg);
+            if (hi > 32) hi = 32;
+            if (lo < hi) fn(g * gw + j, lo, hi, (int)(base + (int64_t)lo * gw - c0));
+        }
+}
+__host__ __device__ inline uint32_t row_get_cols(const uint32_t *row, int64_t c0, int n, int gw) {
+    uint32_t v = 0;
+    for_col_fields(c0, n, gw, [&](int64_t wi, int lo, int hi, int at) {
+        const uint32_t w = row[wi];
+        for (int b = lo; b < hi; ++b, at += gw) v |= ((w >> b) & 1u) << at;
+    });
+    return v;
+}
+__host__ __device__ inline void row_put_cols(uint32_t *row, int64_t c0, int n, int gw, uint32_t v) {
+    for_col_fields(c0, n, gw, [&](int64_t wi, int lo, int hi, int at) {
+        uint32_t m = 0, bits = 0;
+        for (int b = lo; b < hi; ++b, at += gw) {
+            m |= 1u << b;
+            bits |= ((v >> at) & 1u) << b;
+        }
+        row[wi] = (row[wi] & ~m) | bits;
+    });
+}
+
 // Geometry of one pipelined-stencil launch.  Rows are STORAGE rows of a slab
 // buffer: [0,hk) top halo, [hk,hk+H) slab rows, [hk+H,hk+H+hk) bottom halo.
 struct StencilArgs {
@@ -103,5 +141,22 @@ hipError_t launch_clock_probe(unsigned long long *out, const int *stop, unsigned
 // Live-cell count of storage rows [r0,r1), accumulated into *acc.
 hipError_t launch_popcount(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1,
                            int64_t row_bytes, unsigned long long *acc, int bit_layout, hipStream_t s);
+
+// ---- GOL_TORUS: rows of cols + 2·hk storage columns, real column c at c + hk ----
+// Refresh both ghost margins of storage rows [r0, r1): left ghost [0, hk) <- the
+// last hk real columns, right ghost [hk+cols, cols+2hk) <- the first hk real
+// columns.  Only ghost cells are written.  bit_gw: 0 = byte layout, else the
+// bit layout's group width (hk <= 32 there).
+hipError_t launch_wrap_cols(void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t cols, int hk,
+                            int bit_gw, hipStream_t s);
+// launch_interleave_rows for a torus row: linear column c of `lin` (c < ncols)
+// lands at storage column c + shift of the gw-word groups; every other bit of
+// the row's row_words words is stored as 0.
+hipError_t launch_interleave_rows_shift(const uint32_t *lin, uint32_t *out, int64_t pitch_words, int64_t r0,
+                                        int64_t nrows, int64_t row_words, int64_t ncols, int shift, int gw,
+                                        hipStream_t s);
+// Live-cell count of storage columns [c0, c1) of storage rows [r0, r1), added to *acc.
+hipError_t launch_popcount_cols(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t c0,
+                                int64_t c1, unsigned long long *acc, int bit_gw, hipStream_t s);
 
 } // namespace gol

@@ -2876,4 +2876,117 @@ hipError_t launch_popcount(const void *buf, int64_t pitch_bytes, int64_t r0, int
     return hipGetLastError();
 }
 
+// One thread per cell of the column range (the torus ghost margins: at most 64 columns).
+// GW: 0 = byte layout, else the bit layout's group width.
+// (The torus kernels are templates on GW: the compiler then emits them behind every
+// stencil kernel, whose place in the code object stays what it was without them — the
+// row-pair kernels are sensitive to it)
+template <int GW>
+__global__ void popcount_cols_kernel(const uint8_t *__restrict__ buf, int64_t pitch_bytes, int64_t r0,
+                                     int64_t nrows, int64_t c0, int64_t ncols, unsigned long long *acc) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long local = 0;
+    if (t < nrows * ncols) {
+        const uint8_t *row = buf + (r0 + t / ncols) * pitch_bytes;
+        const int64_t c = c0 + t % ncols;
+        local = GW ? (reinterpret_cast<const uint32_t *>(row)[bit_word(c, GW)] >> bit_pos(c, GW)) & 1u
+                   : (row[c] != 0);
+    }
+    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(acc, local);
+}
+
+hipError_t launch_popcount_cols(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t c0,
+                                int64_t c1, unsigned long long *acc, int bit_gw, hipStream_t s) {
+    const int64_t n = (r1 - r0) * (c1 - c0);
+    if (r1 <= r0 || c1 <= c0) return hipSuccess;
+    const auto fn = bit_gw == 4 ? popcount_cols_kernel<4> : bit_gw ? popcount_cols_kernel<2> : popcount_cols_kernel<0>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, static_cast<const uint8_t *>(buf),
+                       pitch_bytes, r0, r1 - r0, c0, c1 - c0, acc);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ torus wrap
+// GOL_TORUS rows carry hk ghost columns on either side of the real ones; the
+// stencil kernels see an ordinary dead-boundary row of cols + 2·hk columns, and
+// after every launch (and every other write of cells) this kernel copies the
+// last hk real columns into the left ghost and the first hk into the right one.
+// Bit layout: one lane per row.  The ghosts are bit fields inside the row's
+// first group and its last one or two, at other bit offsets than their sources
+// (row_get_cols / row_put_cols, gol_internal.h); the access is a pitch-strided
+// column, a few words per lane whatever the width, so waves of 64 rows in blocks
+// of one wave keep the grid as wide as the rows allow.  The stores are
+// read-modify-writes of words that also hold real cells: no other lane touches
+// this row, and the launch is stream-ordered after the kernel that wrote it.
+template <int GW>
+__global__ __launch_bounds__(64) void wrap_cols_bit_kernel(uint32_t *buf, int64_t pitch, int64_t r0, int64_t nrows,
+                                                           int64_t cols, int hk) {
+    constexpr int gw = GW;
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= nrows) return;
+    uint32_t *row = buf + (r0 + t) * pitch;
+    const uint32_t last = row_get_cols(row, cols, hk, gw);   // real columns [cols-hk, cols) at storage + hk
+    const uint32_t first = row_get_cols(row, hk, hk, gw);
+    row_put_cols(row, 0, hk, gw, last);
+    row_put_cols(row, hk + cols, hk, gw, first);
+}
+
+// Byte layout: one thread per ghost byte (the margins may start off a dword boundary).
+template <int GW = 0>
+__global__ __launch_bounds__(256) void wrap_cols_byte_kernel(uint8_t *buf, int64_t pitch, int64_t r0, int64_t nrows,
+                                                             int64_t cols, int hk) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nrows * 2 * hk) return;
+    uint8_t *row = buf + (r0 + t / (2 * hk)) * pitch;
+    const int j = (int)(t % (2 * hk));
+    if (j < hk) row[j] = row[cols + j];   // left ghost <- storage [cols, cols+hk)
+    else row[cols + j] = row[j];          // right ghost [cols+hk, cols+2hk) <- storage [hk, 2hk)
+}
+
+hipError_t launch_wrap_cols(void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t cols, int hk,
+                            int bit_gw, hipStream_t s) {
+    const int64_t nrows = r1 - r0;
+    if (nrows <= 0 || hk <= 0) return hipSuccess;
+    if (cols < hk || (bit_gw && hk > 32)) return hipErrorInvalidValue;   // the sources must be real columns
+    if (bit_gw)
+        hipLaunchKernelGGL(bit_gw == 4 ? wrap_cols_bit_kernel<4> : wrap_cols_bit_kernel<2>,
+                           dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, s, static_cast<uint32_t *>(buf),
+                           pitch_bytes / 4, r0, nrows, cols, hk);
+    else
+        hipLaunchKernelGGL(wrap_cols_byte_kernel<0>, dim3((unsigned)((nrows * 2 * hk + 255) / 256)), dim3(256), 0, s,
+                           static_cast<uint8_t *>(buf), pitch_bytes, r0, nrows, cols, hk);
+    return hipGetLastError();
+}
+
+// Torus init: the generator's linear words (column c at bit c) -> gw-word groups
+// shifted by the left ghost margin.  One thread per output word.
+template <int GW>
+__global__ void interleave_rows_shift_kernel(const uint32_t *__restrict__ lin, uint32_t *__restrict__ out,
+                                             int64_t pitch, int64_t r0, int64_t nrows, int64_t row_words,
+                                             int64_t ncols, int shift) {
+    constexpr int gw = GW;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nrows * row_words) return;
+    const int64_t r = r0 + t / row_words, w = t % row_words;
+    const int64_t base = (w / gw) * 32 * gw + w % gw - shift;   // linear column of bit 0; bit b: base + gw·b
+    const uint32_t *src = lin + r * pitch;
+    uint32_t o = 0;
+    for (int b = 0; b < 32; ++b) {
+        const int64_t c = base + (int64_t)gw * b;
+        if (c >= 0 && c < ncols) o |= ((src[c >> 5] >> (c & 31)) & 1u) << b;
+    }
+    out[r * pitch + w] = o;
+}
+
+hipError_t launch_interleave_rows_shift(const uint32_t *lin, uint32_t *out, int64_t pitch_words, int64_t r0,
+                                        int64_t nrows, int64_t row_words, int64_t ncols, int shift, int gw,
+                                        hipStream_t s) {
+    const int64_t n = nrows * row_words;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gw == 4 ? interleave_rows_shift_kernel<4> : interleave_rows_shift_kernel<2>,
+                       dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lin, out, pitch_words, r0, nrows, row_words,
+                       ncols, shift);
+    return hipGetLastError();
+}
+
 } // namespace gol

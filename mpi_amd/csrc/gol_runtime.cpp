@@ -209,6 +209,12 @@ struct gol_ctx {
     int64_t active_rows = 0, active_cols = 0;
     int perm_m = 1;              // MESH_COMPAT: column blocks stored in reverse order (see validate)
     int64_t perm_L = 0;          // columns per block
+    // GOL_TORUS: a row is stored as scols = cols + 2·xoff columns, real column c at c + xoff
+    // between two ghost margins of xoff = hk columns (wrap_rows); the kernels run the
+    // widened dead-boundary row.  Every other boundary: xoff = 0, scols = cols.
+    bool torus = false;
+    int xoff = 0;
+    int64_t scols = 0;
     int64_t pitch_bytes = 0;     // row pitch
     int64_t row_bytes = 0;       // bytes per row that may hold cells
     int nunits = 0;              // stencil units (bit words / byte dwords) per row
@@ -333,7 +339,7 @@ int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // Storage column of logical column lc (MESH_COMPAT: reversed column blocks).
 int64_t phys_col(const gol_ctx *c, int64_t lc) {
-    if (c->perm_m <= 1) return lc;
+    if (c->perm_m <= 1) return lc + c->xoff;   // (GOL_TORUS: behind the left ghost margin)
     const int64_t cy = lc / c->perm_L;
     return (c->perm_m - 1 - cy) * c->perm_L + (lc - cy * c->perm_L);
 }
@@ -360,12 +366,16 @@ void slab_plan(int64_t rows, int world, int rank, int64_t *row0, int64_t *nrows)
 
 int64_t storage_rows(const gol_ctx *c, const Slab &s) { return s.H + 2 * c->hk; }
 
+// The halo path of one_step (comm stream, exchange, boundary bands): several slabs, or a
+// torus, whose single slab is a ring of one.
+bool ring_path(const gol_ctx *c) { return c->nslabs > 1 || c->torus; }
+
 int validate(gol_ctx *c, int64_t rows, int64_t cols, int nslabs, int layout, int boundary, int mesh_m,
              int k) {
     if (rows < 1 || cols < 1) return fail(c, GOL_EINVAL, "rows/cols must be positive");
     if (rows > (1LL << 30) || cols > (1LL << 31) - 64) return fail(c, GOL_EINVAL, "grid too large");
     if (layout != GOL_LAYOUT_BIT && layout != GOL_LAYOUT_BYTE) return fail(c, GOL_EINVAL, "bad layout");
-    if (boundary < GOL_DEAD || boundary > GOL_MESH_COMPAT) return fail(c, GOL_EINVAL, "bad boundary");
+    if (boundary < GOL_DEAD || boundary > GOL_TORUS) return fail(c, GOL_EINVAL, "bad boundary");
     if (k < 1 || (k > 8 && !(layout == GOL_LAYOUT_BYTE ? bytebit_supported(k) : bit_depth_supported(k))))
         return fail(c, GOL_EINVAL,
                     "tblock_k must be in [1,8] (bit layout: also 16 or 32; byte layout: also 12, 16, 20, 24, 28, 32, "
@@ -384,7 +394,15 @@ int validate(gol_ctx *c, int64_t rows, int64_t cols, int nslabs, int layout, int
         return fail(c, GOL_EINVAL, "SERIAL_COMPAT needs rows, cols >= 2");
     // every wave's buffer window (>= 2k+8 rows) must stay far below the kernels'
     // out-of-range offset (2^30 B): rows of at most ~2^29/(2k+8) bytes
-    const int64_t row_b = layout == GOL_LAYOUT_BIT ? (cols + 31) / 32 * 4 : cols;
+    // GOL_TORUS: k ghost columns per side whose sources must be real columns, and a ring of
+    // slabs that each send k rows of their own either way (a single slab to itself)
+    if (boundary == GOL_TORUS && cols < k)
+        return fail(c, GOL_EINVAL, "TORUS needs cols >= tblock_k (%lld < %d)", (long long)cols, k);
+    if (boundary == GOL_TORUS && rows / nslabs < k)
+        return fail(c, GOL_EINVAL, "TORUS needs every slab (a single one too) to hold at least tblock_k=%d rows: %lld",
+                    k, (long long)(rows / nslabs));
+    const int64_t wide = boundary == GOL_TORUS ? cols + 2 * k : cols;   // the stored row
+    const int64_t row_b = layout == GOL_LAYOUT_BIT ? (wide + 31) / 32 * 4 : wide;
     if (row_b * (2 * k + 8) >= (1LL << 28))
         return fail(c, GOL_EUNSUPPORTED, "rows of %lld bytes are too wide for tblock_k=%d", (long long)row_b, k);
     const int64_t hmin = rows / nslabs;
@@ -405,16 +423,16 @@ constexpr int64_t kPitchPadBit = 128, kPitchPadByte = 512;
 
 void set_geometry(gol_ctx *c) {
     c->active_rows = c->boundary == GOL_SERIAL_COMPAT ? c->rows - 1 : c->rows;
-    c->active_cols = c->boundary == GOL_SERIAL_COMPAT ? c->cols - 1 : c->cols;
+    c->active_cols = c->boundary == GOL_SERIAL_COMPAT ? c->cols - 1 : c->scols;
     if (c->layout == GOL_LAYOUT_BIT) {
         // 64-column groups of 2 words, rows padded to 128-column blocks (gol_internal.h)
-        const int64_t words = (c->cols + 127) / 128 * 4;
+        const int64_t words = (c->scols + 127) / 128 * 4;
         c->pitch_bytes = round_up(words, 64) * 4 + kPitchPadBit;
         c->row_bytes = words * 4;
         c->nunits = (int)((c->active_cols + 127) / 128 * 4);
         c->last_mask = 0;
     } else {
-        const int64_t dws = (c->cols + 3) / 4;
+        const int64_t dws = (c->scols + 3) / 4;
         c->pitch_bytes = round_up(dws, 64) * 4 + kPitchPadByte;
         c->row_bytes = dws * 4;
         c->nunits = (int)((c->active_cols + 3) / 4);
@@ -436,7 +454,7 @@ int alloc_slab(gol_ctx *c, Slab &s) {
     // on top of the first upload (GPUTEST_r04: test_mesh_random[byte-1026-3]).
     for (int i = 0; i < 2; ++i) HIPCHK(c, hipMemsetAsync(s.buf[i], 0, bytes, s.comp));
     HIPCHK(c, tr_ssync(c, s.comp));
-    if (c->nslabs == 1) {
+    if (!ring_path(c)) {
         // one slab has no halo path: one stream.  (A process gets few hardware
         // queues — GPU_MAX_HW_QUEUES, 4 by default — and streams beyond them
         // share one: work queued behind a long kernel of another stream waits
@@ -457,7 +475,8 @@ int alloc_slab(gol_ctx *c, Slab &s) {
     }
     HIPCHK(c, hipEventCreate(&s.ev_start));
     HIPCHK(c, hipEventCreate(&s.ev_stop));
-    const bool top = s.index == 0, bottom = s.index == c->nslabs - 1;
+    // (a torus has no dead side: every slab is an interior slab of the ring)
+    const bool top = s.index == 0 && !c->torus, bottom = s.index == c->nslabs - 1 && !c->torus;
     s.row_lo = top ? c->hk : 0;
     s.row_hi = (int)(c->hk + s.H + (bottom ? 0 : c->hk));
     if (bottom && c->boundary == GOL_SERIAL_COMPAT) s.row_hi -= 1;   // global row rows-1 is dead
@@ -487,6 +506,7 @@ void free_slab(Slab &s) {
 }
 
 Slab *find_slab(gol_ctx *c, int index) {
+    if (c->torus) index = (index + c->nslabs) % c->nslabs;   // the ring: slab -1 is the last one
     for (auto &s : c->slabs)
         if (s.index == index) return &s;
     return nullptr;
@@ -530,6 +550,17 @@ int enable_split(gol_ctx *c, Slab &s, int parts) {
 }
 
 // --------------------------------------------------------------- stencil launch
+
+// GOL_TORUS: refresh the ghost margins of storage rows [r0, r1) of buffer b on stream st
+// (after anything that wrote cells there; nothing to do for the other boundaries).
+int wrap_rows(gol_ctx *c, Slab &s, int b, int64_t r0, int64_t r1, hipStream_t st) {
+    if (!c->torus || r1 <= r0) return GOL_OK;
+    tr_op(c, TR_READ, st, nullptr, s.index, b, r0, r1);
+    tr_op(c, TR_WRITE, st, nullptr, s.index, b, r0, r1);
+    HIPCHK(c, launch_wrap_cols(s.buf[b], c->pitch_bytes, r0, r1, c->cols, c->xoff,
+                               c->layout == GOL_LAYOUT_BIT ? c->gw : 0, st));
+    return GOL_OK;
+}
 
 int launch_stencil(gol_ctx *c, Slab &s, int gens, int r0, int r1, hipStream_t st, bool timed) {
     if (r1 <= r0) return GOL_OK;
@@ -592,7 +623,9 @@ int launch_stencil(gol_ctx *c, Slab &s, int gens, int r0, int r1, hipStream_t st
             HIPCHK(c, launch_byte_pipe(a, gens, st));
     }
     if (tl) HIPCHK(c, tr_record(c, tl->b, st));
-    return GOL_OK;
+    // GOL_TORUS: the rows just written get their ghost margins back on the same stream,
+    // before the caller records its event — it touches only this launch's rows
+    return wrap_rows(c, s, c->cur ^ 1, r0, r1, st);
 }
 
 // GOL_OPT_COMM_TIMING: harvest the oldest event quad of slab s (blocks for it).
@@ -654,6 +687,24 @@ int exchange(gol_ctx *c, Slab &s, int k, int64_t t) {
         if (grow)
             if (int rc = wait_interior(c, s, s.comm, pp)) return rc;
         const int64_t hk = c->hk, H = s.H;
+        if (c->torus) {
+            // the ring: peers (rank ± 1) mod world.  With two ranks both peers are the same
+            // rank, and a pair's sends and receives match in order: every rank sends its top
+            // rows first and receives its bottom halo first, so the peer's top rows land in my
+            // bottom halo.  (One rank: transport NONE, the self copies of the PEER path below.)
+            const int up = (c->rank + c->world - 1) % c->world, dn = (c->rank + 1) % c->world;
+            tr_op(c, TR_READ, s.comm, nullptr, s.index, c->cur, hk, hk + k);
+            tr_op(c, TR_READ, s.comm, nullptr, s.index, c->cur, hk + H - k, hk + H);
+            tr_op(c, TR_WRITE, s.comm, nullptr, s.index, c->cur, hk + H, hk + H + k);
+            tr_op(c, TR_WRITE, s.comm, nullptr, s.index, c->cur, hk - k, hk);
+            NCCLCHK(c, R.GroupStart());
+            NCCLCHK(c, R.Send(top_rows, nbytes, ncclUint8, up, c->comm, s.comm));
+            NCCLCHK(c, R.Send(bot_rows, nbytes, ncclUint8, dn, c->comm, s.comm));
+            NCCLCHK(c, R.Recv(bot_halo, nbytes, ncclUint8, dn, c->comm, s.comm));
+            NCCLCHK(c, R.Recv(top_halo, nbytes, ncclUint8, up, c->comm, s.comm));
+            NCCLCHK(c, R.GroupEnd());
+            return GOL_OK;
+        }
         if (c->rank > 0) {
             tr_op(c, TR_READ, s.comm, nullptr, s.index, c->cur, hk, hk + k);
             tr_op(c, TR_WRITE, s.comm, nullptr, s.index, c->cur, hk - k, hk);
@@ -751,7 +802,7 @@ int tune_mark(gol_ctx *c, int i, int p) {
     for (size_t si = 0; si < c->slabs.size(); ++si) {
         Slab &s = c->slabs[si];
         HIPCHK(c, hipSetDevice(s.device));
-        if (c->nslabs > 1 || s.nx) HIPCHK(c, tr_wait(c, s.comp, s.ev_bnd[p]));
+        if (ring_path(c) || s.nx) HIPCHK(c, tr_wait(c, s.comp, s.ev_bnd[p]));
         if (int rc = join_parts(c, s, s.comp)) return rc;
         HIPCHK(c, tr_record(c, c->tune_ev[si * per + i], s.comp));
     }
@@ -961,7 +1012,7 @@ int one_step(gol_ctx *c, int k) {
         }
         return GOL_OK;
     };
-    if (c->nslabs == 1) {
+    if (!ring_path(c)) {
         Slab &s = c->slabs[0];
         HIPCHK(c, hipSetDevice(s.device));
         const int lo = hk, hi = (int)(hk + s.H), np = nparts(s, lo, hi);
@@ -1003,7 +1054,7 @@ int one_step(gol_ctx *c, int k) {
             // boundary bands on the comm stream, after the exchange
             if (t > 0)
                 if (int rc = wait_interior(c, s, s.comm, pp)) return rc;
-            if (c->transport == GOL_XPORT_PEER) {
+            if (c->transport != GOL_XPORT_RCCL) {   // (PEER, or a torus ring of one)
                 // neighbours must have pulled our previous edge rows before we overwrite them
                 Slab *up = find_slab(c, s.index - 1), *dn = find_slab(c, s.index + 1);
                 if (up) HIPCHK(c, tr_wait(c, s.comm, up->ev_exch[p]));
@@ -1260,17 +1311,23 @@ int run_units(gol_ctx *c, Slab &s, UnitPlan &plan) {
     void *target = bit ? s.buf[c->cur ^ 1] : s.buf[c->cur];
     hipError_t e = launch_init_units(d_units, (int)plan.units.size(), d_mats, T, seg, target, c->pitch_bytes, bit,
                                      s.comp);
-    if (e == hipSuccess && bit)
+    if (e == hipSuccess && bit && c->torus)   // (the units sit at linear column 0: see init_slab)
+        e = launch_interleave_rows_shift(static_cast<const uint32_t *>(target), static_cast<uint32_t *>(s.buf[c->cur]),
+                                         c->pitch_bytes / 4, c->hk, s.H, c->row_bytes / 4, c->cols, c->xoff, c->gw,
+                                         s.comp);
+    else if (e == hipSuccess && bit)
         e = launch_interleave_rows(static_cast<const uint32_t *>(target), static_cast<uint32_t *>(s.buf[c->cur]),
                                    c->pitch_bytes / 4, c->hk, s.H, (c->cols + 127) / 128, c->gw, s.comp);
     if (e == hipSuccess && bit)
         e = hipMemsetAsync(target, 0, (size_t)storage_rows(c, s) * c->pitch_bytes, s.comp);
+    int wrapped = GOL_OK;
+    if (e == hipSuccess) wrapped = wrap_rows(c, s, c->cur, c->hk, c->hk + s.H, s.comp);
     hipError_t e2 = tr_ssync(c, s.comp);
     (void)hipFree(d_units);
     (void)hipFree(d_mats);
     HIPCHK(c, e);
     HIPCHK(c, e2);
-    return GOL_OK;
+    return wrapped;
 }
 
 int init_slab(gol_ctx *c, Slab &s, int mode, uint32_t seed) {
@@ -1298,10 +1355,14 @@ int init_slab(gol_ctx *c, Slab &s, int mode, uint32_t seed) {
     };
     // logical columns [lcol0, lcol0+len) of rows [g0, g1), draw `first_offset` at (g0, lcol0):
     // one unit run per storage-contiguous piece
+    // (a torus bit board's units go to linear column 0 of the spare buffer; the regrouping
+    // pass moves them behind the ghost margin, which need not be a multiple of 32 columns)
+    const bool unshifted = c->torus && c->layout == GOL_LAYOUT_BIT;
     bool misaligned = false;
     auto add_cols = [&](uint32_t stream_seed, uint64_t first_offset, uint64_t stride, int64_t g0_, int64_t g1_,
                         int64_t lcol0, int64_t len) {
         for_col_runs(c, lcol0, len, [&](int64_t lc, int64_t pc, int64_t n) {
+            if (unshifted) pc = lc;
             // the bit-layout writer stores whole 32-column words: runs must start on one
             if (c->layout == GOL_LAYOUT_BIT && pc % 32 != 0) misaligned = true;
             add_units(stream_seed, first_offset + (uint64_t)(lc - lcol0), stride, g0_, g1_, (int32_t)pc, (int32_t)n);
@@ -1309,8 +1370,10 @@ int init_slab(gol_ctx *c, Slab &s, int mode, uint32_t seed) {
         });
     };
     const int64_t g0 = s.row0, g1 = s.row0 + s.H;
+    if (c->torus && mode != GOL_INIT_STREAM)
+        return fail(c, GOL_EUNSUPPORTED, "a TORUS board takes GOL_INIT_STREAM only (init mode %d)", mode);
     if (mode == GOL_INIT_STREAM) {
-        add_cols(seed, (uint64_t)g0 * c->cols, c->cols, g0, g1, 0, c->active_cols);
+        add_cols(seed, (uint64_t)g0 * c->cols, c->cols, g0, g1, 0, c->torus ? c->cols : c->active_cols);
         if (c->boundary == GOL_SERIAL_COMPAT) {   // keep the inactive last row dead
             const int64_t gl = std::min(g1, c->rows - 1);
             plan.units.erase(std::remove_if(plan.units.begin(), plan.units.end(),
@@ -1379,7 +1442,7 @@ int upload_piece(gol_ctx *c, Slab &s, int64_t r0, int64_t r1, int64_t col0, int6
         HIPCHK(c, hipSetDevice(s.device));
         tr_op(c, TR_WRITE, s.comp, nullptr, s.index, c->cur, srow, srow + nr);
         HIPCHK(c, hipMemcpyAsync(b.dtmp, b.pinned, (size_t)(nr * ncols), hipMemcpyHostToDevice, s.comp));
-        return for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
+        int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
             const uint8_t *cells = b.dtmp + (lc - col0);
             if (c->layout == GOL_LAYOUT_BYTE) {
                 uint8_t *d = board + srow * c->pitch_bytes + pc;
@@ -1392,6 +1455,7 @@ int upload_piece(gol_ctx *c, Slab &s, int64_t r0, int64_t r1, int64_t col0, int6
             }
             return GOL_OK;
         });
+        return rc ? rc : wrap_rows(c, s, c->cur, srow, srow + nr, s.comp);
     };
     int rc = enqueue();
     if (rc) {
@@ -1540,8 +1604,8 @@ int text_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols
             const int64_t srow = c->hk + (a - s.row0);
             char *pin = t.pinned[i & 1];
             if (!upload) {
-                HIPCHK(c, launch_format_text(cur, c->pitch_bytes, bit ? c->gw : 0, srow, col0, nr, ncols, c->perm_m,
-                                             c->perm_L, t.dtext, s.comm));
+                HIPCHK(c, launch_format_text(cur, c->pitch_bytes, bit ? c->gw : 0, srow, col0 + c->xoff, nr, ncols,
+                                             c->perm_m, c->perm_L, t.dtext, s.comm));
                 HIPCHK(c, hipMemcpyAsync(pin, t.dtext, (size_t)bytes, hipMemcpyDeviceToHost, s.comm));
             } else {
                 HIPCHK(c, hipMemcpyAsync(t.dtext, pin, (size_t)bytes, hipMemcpyHostToDevice, s.comm));
@@ -1561,9 +1625,10 @@ int text_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols
                     });
                     if (rc2) return rc2;
                 } else {
-                    HIPCHK(c, launch_parse_text(t.dtext, nr, ncols, cur + srow * c->pitch_bytes + col0,
+                    HIPCHK(c, launch_parse_text(t.dtext, nr, ncols, cur + srow * c->pitch_bytes + col0 + c->xoff,
                                                 c->pitch_bytes, base, t.derr, s.comm));
                 }
+                if (int rc2 = wrap_rows(c, s, c->cur, srow, srow + nr, s.comm)) return rc2;
             }
             HIPCHK(c, tr_record(c, t.ev[i & 1], s.comm));
             return GOL_OK;
@@ -1642,6 +1707,9 @@ int common_create(gol_ctx *c, int64_t rows, int64_t cols, int layout, int bounda
     }
     c->K = k;
     c->hk = k;
+    c->torus = boundary == GOL_TORUS;
+    c->xoff = c->torus ? k : 0;
+    c->scols = cols + 2 * c->xoff;
     c->gw = layout == GOL_LAYOUT_BIT ? bit_group_words(k) : 2;
     // Geometry defaults measured on MI355X at 131072² (tools/tune.py):
     // k <= 4 is HBM-bound and wants many short chunks; k >= 6 is VALU-bound and
@@ -1726,8 +1794,8 @@ int gol_create(gol_ctx **out, int64_t rows, int64_t cols, int n_gpus, int layout
         }
     }
     // peer access between distinct devices (xGMI); same-device copies need none
-    for (int i = 0; i + 1 < n_gpus; ++i) {
-        const int a = c->slabs[i].device, b = c->slabs[i + 1].device;
+    for (int i = 0; i + 1 < n_gpus || (c->torus && i < n_gpus); ++i) {   // (torus: the last slab with the first)
+        const int a = c->slabs[i].device, b = c->slabs[(i + 1) % n_gpus].device;
         if (a != b) {
             (void)hipSetDevice(a);
             (void)hipDeviceEnablePeerAccess(b, 0);
@@ -2008,10 +2076,19 @@ int gol_popcount(gol_ctx *c, int64_t *live) {
         HIPCHK(c, hipMemsetAsync(s.d_count, 0, sizeof(unsigned long long), s.comp));
         HIPCHK(c, launch_popcount(s.buf[c->cur], c->pitch_bytes, c->hk, c->hk + s.H, c->row_bytes, s.d_count,
                                   c->layout == GOL_LAYOUT_BIT, s.comp));
-        unsigned long long v = 0;
+        unsigned long long v = 0, ghosts = 0;
         HIPCHK(c, hipMemcpyAsync(&v, s.d_count, sizeof v, hipMemcpyDeviceToHost, s.comp));
+        if (c->torus) {   // the row popcount took the ghost margins (copies of real cells) along
+            const int gw = c->layout == GOL_LAYOUT_BIT ? c->gw : 0;
+            HIPCHK(c, hipMemsetAsync(s.d_count, 0, sizeof(unsigned long long), s.comp));
+            HIPCHK(c, launch_popcount_cols(s.buf[c->cur], c->pitch_bytes, c->hk, c->hk + s.H, 0, c->xoff, s.d_count,
+                                           gw, s.comp));
+            HIPCHK(c, launch_popcount_cols(s.buf[c->cur], c->pitch_bytes, c->hk, c->hk + s.H, c->xoff + c->cols,
+                                           c->scols, s.d_count, gw, s.comp));
+            HIPCHK(c, hipMemcpyAsync(&ghosts, s.d_count, sizeof ghosts, hipMemcpyDeviceToHost, s.comp));
+        }
         HIPCHK(c, tr_ssync(c, s.comp));
-        total += (int64_t)v;
+        total += (int64_t)v - (int64_t)ghosts;
     }
     *live = total;
     return GOL_OK;

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 LAYOUT = {"byte": 0, "bit": 1}
-BOUNDARY = {"dead": 0, "serial_compat": 1, "mesh_compat": 2}
+BOUNDARY = {"dead": 0, "serial_compat": 1, "mesh_compat": 2, "torus": 3}
 INIT = {"stream": 0, "serial": 1, "mesh": 2}
 SERIAL_SEED = 1804289383
 
