@@ -40,11 +40,13 @@ extern "C" {
 #define GOL_LAYOUT_BYTE 0 /* 1 byte per cell (0/1); row pitch = 256·n + 512 B (channel spread) */
 #define GOL_LAYOUT_BIT 1  /* 1 bit per cell; column groups of G u32 words, column 32G·g+G·j+w in
                              word G·g+w, bit j (interleaved: neighbours share a bit); G = 4 for
-                             tblock_k = 8, else 2.  Never visible through this ABI (host I/O is
+                             tblock_k >= 8 (8, 16, 32), else 2.  Never visible through this ABI (host I/O is
                              0/1 bytes) */
 
 /* Boundary conventions */
-#define GOL_DEAD 0          /* non-periodic B3/S23 (main.cpp, P=1; periods {0,0} main.cpp:243) */
+#define GOL_DEAD 0          /* non-periodic (main.cpp, P=1; periods {0,0} main.cpp:243): everything
+                               outside the grid is permanently dead; it does not evolve, whatever the
+                               rule (gol_set_rule), which is why B0 rules are refused */
 #define GOL_SERIAL_COMPAT 1 /* main_serial.cpp:45-71: DEAD on the top-left (n-1)², last row/col 0 */
 #define GOL_MESH_COMPAT 2   /* main.cpp on a √P×√P mesh, P=mesh_m²: swapped column halos
                                (main.cpp:51-54); any layout and tblock_k (stored as a dead-boundary
@@ -90,12 +92,12 @@ extern "C" {
 #define GOL_OPT_WORDS_PER_LANE 3 /* retired in 0.2 (lane widths are fixed per kernel): set is a no-op */
 #define GOL_OPT_OVERLAP 4       /* multi-slab: 1 = interior kernel overlapped with halo exchange (default) */
 #define GOL_OPT_BYTE_CORE 5     /* byte layout: 1 = bit-sliced core where tblock_k is 4, 8, 12, 16, 20,
-                                   24, 28, 32, 48 or 64 (default; the kernel per depth is the library's
+                                   24, 28, 32, 48, 56 or 64 (default; the kernel per depth is the library's
                                    pick); 2 = its one-wave-per-strip kernel (k <= 32); 3 = its chain
                                    kernel (a workgroup of 2-4 waves per strip splitting the stages,
                                    k = 24, 32, 48, 64; 48 and 64 always run it); 4 = the byte board
                                    through the bit board's pair waves (a pack wave, k / 8 pair waves,
-                                   an unpack wave per strip; k = 16, 32, 48, other depths as 1);
+                                   an unpack wave per strip; k = 16, 24, 32, 48, 56, other depths as 1);
                                    0 = byte-SWAR kernel (tblock_k <= 8) */
 #define GOL_OPT_SPLIT 6         /* retired in 0.2 (boundary bands are always split off): set is a no-op */
 #define GOL_OPT_TEXT_BLOCK_BYTES 10 /* snapshot text: bytes per pinned staging block (default 64 MiB) */
@@ -120,7 +122,7 @@ extern "C" {
                                      next step's parts start while this step's parts drain (a slab
                                      takes the most parts with >= 32·tblock_k interior rows each,
                                      down to one).
-                                     Default 2 for bit layout at tblock_k = 8 with at most 4 slabs per
+                                     Default 2 for bit layout at tblock_k >= 8 (8, 16, 32) with at most 4 slabs per
                                      device whose 3 streams each (+ the clock probe's) fit the process's
                                      hardware queues (3 x slabs + 1 <= GPU_MAX_HW_QUEUES, HIP default 4:
                                      one slab per device), 1 otherwise.  Setting it synchronises the context; with no
@@ -145,6 +147,11 @@ extern "C" {
                                     time beside the real one (bench.py's N > 1 line); 1 = default.
                                     RCCL mode: collective (set it alike on every rank) */
 
+#define GOL_OPT_RULE_KERNEL 16  /* 0 (default): B3/S23 runs the tuned kernels; 1: every rule, B3/S23 too,
+                                   runs the rule-generic kernel (a context gol_set_rule supports; others
+                                   GOL_EUNSUPPORTED).  Setting it synchronises the context.  RCCL mode:
+                                   local state, results do not depend on it */
+
 typedef struct gol_ctx gol_ctx;
 
 /* Single process.  The grid is cut into n_gpus row slabs; slab s lives on HIP
@@ -167,6 +174,35 @@ int gol_slab_plan(int64_t rows, int world, int rank, int64_t *row0, int64_t *nro
 
 int gol_set_option(gol_ctx *ctx, int option, int64_t value);
 int gol_get_option(gol_ctx *ctx, int option, int64_t *value);
+
+/* Life-like (outer-totalistic) rules in B/S notation.  Bit n (0..8) of `birth`: a
+ * dead cell with n live neighbours, out of 8, is born; bit n of `survive`: a live
+ * cell with n live neighbours stays alive.  A new context runs B3/S23
+ * (birth = 1<<3, survive = (1<<2)|(1<<3)), the one rule the reference knows
+ * (main.cpp:79-91), on the kernels tuned for it; any other rule runs the
+ * rule-generic kernel.
+ *   gol_parse_rule  (host only, no context) "B36/S23" or "S23/B36" in either letter
+ *                   case, or the legacy survive/birth form "23/3"; a digit list may
+ *                   be empty ("B2/S"); digits are 0..8, each at most once.  Anything
+ *                   else is GOL_EINVAL.  It does not judge the rule (B0 parses).
+ *   gol_set_rule    any time between steps; synchronises the context (as
+ *                   GOL_OPT_INTERIOR_SPLIT does) and holds from the next gol_step.
+ *                   GOL_EINVAL: bits above 8, or B0 (birth & 1) — cells outside the
+ *                   grid, pad columns and rows outside a slab's live rows are dead at
+ *                   every generation, and the runtime relies on dead staying dead in
+ *                   empty space.  A rule other than B3/S23 (and GOL_OPT_RULE_KERNEL = 1)
+ *                   needs GOL_LAYOUT_BIT, tblock_k 1..7 (2-word groups), GOL_DEAD or
+ *                   GOL_TORUS; any slab count, either transport.  GOL_EUNSUPPORTED
+ *                   naming the limit otherwise: the byte layout, tblock_k >= 8, and
+ *                   GOL_SERIAL_COMPAT / GOL_MESH_COMPAT (they reproduce the reference
+ *                   program, which knows one rule); the context stays usable.
+ *                   Setting B3/S23 itself is GOL_OK on every context.
+ *                   RCCL mode: the rule is local state, so the call is COLLECTIVE:
+ *                   set it alike on every rank, between the same two steps.
+ *   gol_get_rule    the rule in force. */
+int gol_parse_rule(const char *text, uint32_t *birth, uint32_t *survive);
+int gol_set_rule(gol_ctx *ctx, uint32_t birth, uint32_t survive);
+int gol_get_rule(gol_ctx *ctx, uint32_t *birth, uint32_t *survive);
 
 /* On-device glibc-rand initialisation with jump-ahead, bit-identical to the
  * reference's initializeBoard (main.cpp:68-77, main_serial.cpp:34-43). */

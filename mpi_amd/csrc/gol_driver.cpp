@@ -23,6 +23,11 @@
 //   --layout bit|byte       cell layout (default: bit; byte when --procs P has
 //                           blocks of cols/√P not a multiple of 32 columns)
 //   -k K                    generations fused per launch (default 1)
+//   --rule B36/S23          a life-like rule in B/S notation (gol_parse_rule: also
+//                           S23/B36 and the legacy 23/3) instead of B3/S23; with
+//                           --mode dead|torus, --layout bit and -k 1..7 (the mpi and
+//                           serial modes reproduce the reference, which knows one
+//                           rule).  Snapshots and timing files as without it
 //   --save / --no-save      write snapshots every gap generations
 //                           (default: on for serial, off for mpi/dead as in main.cpp:208)
 //   --seed S                override the srand seed
@@ -137,6 +142,7 @@ struct Opts {
     int from = -1;        // --from ITER: the saved iteration to continue from
     bool rccl = false, same_device = false;
     std::string rccl_lib;
+    std::string rule;     // --rule: B/S notation (empty: B3/S23 on the tuned kernels)
 };
 
 // One rank of --rccl: its context and what it reports.
@@ -173,6 +179,7 @@ int main(int argc, char **argv) {
         else if (a == "--gpus") o.gpus = atoi(next());
         else if (a == "--layout") o.layout = next();
         else if (a == "-k") o.k = atoi(next());
+        else if (a == "--rule") o.rule = next();
         else if (a == "--save") o.save = 1;
         else if (a == "--no-save") o.save = 0;
         else if (a == "--seed") o.seed = atoll(next());
@@ -239,6 +246,15 @@ int main(int argc, char **argv) {
     } else {
         die("--mode must be mpi, serial, dead or torus");
     }
+    uint32_t birth = 0, survive = 0;
+    if (!o.rule.empty()) {
+        if (gol_parse_rule(o.rule.c_str(), &birth, &survive) != GOL_OK)
+            die("--rule must be in B/S notation, such as B36/S23, S23/B36 or 23/3");
+        if (o.mode != "dead" && o.mode != "torus")
+            die("--rule needs --mode dead or torus (the mpi and serial modes reproduce the reference program, "
+                "which knows B3/S23 only)");
+        if (layout != GOL_LAYOUT_BIT) die("--rule needs --layout bit (the byte layout computes B3/S23 only)");
+    }
     if (o.seed >= 0) seed = (uint32_t)o.seed;
     if (gap <= 0 && save) die("iteration_gap must be positive when saving");
 
@@ -285,6 +301,7 @@ int main(int argc, char **argv) {
         else
             check(nullptr, gol_create(&ctx, rows, cols, o.gpus, layout, boundary, m, o.k), "gol_create");
         rk[i].ctx = ctx;
+        if (!o.rule.empty()) check(ctx, gol_set_rule(ctx, birth, survive), "gol_set_rule");   // (-k >= 8: its message)
         // launches are counted on the host (gol_kernel_time without GOL_OPT_KERNEL_TIMING): no event pair
         // per launch inside the timed region
         if (o.resume.empty()) {

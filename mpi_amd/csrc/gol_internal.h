@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gol_rule.h"
+
 namespace gol {
 
 // Bit layout = interleaved groups of gw u32 words (gw = 2 or 4): a group holds
@@ -83,6 +85,10 @@ int bit_group_words(int K);
 // waves on 4-word groups), a.gw-word groups.
 bool bit_depth_supported(int gens);
 hipError_t launch_bit_pipe(const StencilArgs &a, int gens, hipStream_t s);
+// Bit layout, any life-like rule (gol_rule.h; B3/S23 too): the rule-generic
+// pipeline, gens = 1..7 on 2-word groups.  A launch it cannot serve is an error.
+bool bit_rule_supported(int gens, int gw);
+hipError_t launch_bit_rule(const StencilArgs &a, int gens, const RuleMasks &rule, hipStream_t s);
 // Byte layout, `gens` generations fused (1 <= gens <= 8), 16 cells per lane.
 hipError_t launch_byte_pipe(const StencilArgs &a, int gens, hipStream_t s);
 // Byte layout with the bit-sliced core (bytebit_pipe_kernel): byte-per-cell in

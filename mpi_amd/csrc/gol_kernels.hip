@@ -26,6 +26,8 @@
 //                 k <= 8 when asked for.
 //  * bit layout, k = 16 / 32: bit_chain_kernel, a chain of row-pair waves per
 //                 strip handing rows through LDS (the headline at k = 16).
+//  * bit layout, life-like rules other than B3/S23 (k <= 7): bit_rule_kernel, the
+//                 bit pipeline with the table-driven stage of gol_rule.h (end of file).
 #include "gol_internal.h"
 
 #include <algorithm>
@@ -431,6 +433,19 @@ __device__ __forceinline__ uint32_t life_bits_full(uint32_t a0, uint32_t a1, uin
     return __builtin_amdgcn_bitop3_b32(m, u, alive, 0xE0);              // m & (u | alive)
 }
 
+// The rule stage of the register pipeline below is a functor, apply<EDGE>(the
+// life_bits arguments).  This one is B3/S23 as the tuned truth tables above: no
+// state, so the instantiations that name it compile to what they did when the
+// two calls stood in bit_phase.  (The other one: RuleStage, at the end of the file.)
+struct LifeStage {
+    template <bool EDGE>
+    __device__ __forceinline__ uint32_t apply(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
+                                              uint32_t c1, uint32_t alive, uint32_t mask) const {
+        if constexpr (EDGE) return life_bits(a0, a1, b0, b1, c0, c1, alive, mask);
+        else return life_bits_full(a0, a1, b0, b1, c0, c1, alive);
+    }
+};
+
 // The K-stage register pipeline.  Stage g keeps a 3-row window of generation
 // g (the horizontal sums h0/h1 and the alive plane c of each row) and emits
 // generation g+1 one row behind its input.  The K stages form NC chains of CL
@@ -453,9 +468,9 @@ struct BitState {
 
 // EDGE: chunks near the dead row boundary or strips with cells outside the
 // grid (per-row validity selects and column masks); otherwise neither.
-template <int V, int K, int CL, int RING, int AUX, bool EDGE, int P, int G>
+template <int V, int K, int CL, int RING, int AUX, bool EDGE, int P, int G, typename ST = LifeStage>
 __device__ __forceinline__ void bit_phase(BitState<V, K, CL, RING> &S, const Strip<V> &st, const StencilArgs &a,
-                                          int it, int N) {
+                                          int it, int N, const ST &stage = ST{}) {
     constexpr int NC = BitState<V, K, CL, RING>::NC;
     constexpr int D = NC - 1;
     constexpr int PD = RING / 2;      // prefetch distance
@@ -487,12 +502,9 @@ __device__ __forceinline__ void bit_phase(BitState<V, K, CL, RING> &S, const Str
             const bool valid = !EDGE || (x >= a.row_lo && x < a.row_hi);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                const uint32_t o =
-                    EDGE ? life_bits(GOL_W(h0, g, A, j), GOL_W(h1, g, A, j), GOL_W(h0, g, B, j), GOL_W(h1, g, B, j),
-                                     GOL_W(h0, g, C, j), GOL_W(h1, g, C, j), GOL_W(c, g, B, j), st.mask[j])
-                         : life_bits_full(GOL_W(h0, g, A, j), GOL_W(h1, g, A, j), GOL_W(h0, g, B, j),
-                                          GOL_W(h1, g, B, j), GOL_W(h0, g, C, j), GOL_W(h1, g, C, j),
-                                          GOL_W(c, g, B, j));
+                const uint32_t o = stage.template apply<EDGE>(
+                    GOL_W(h0, g, A, j), GOL_W(h1, g, A, j), GOL_W(h0, g, B, j), GOL_W(h1, g, B, j),
+                    GOL_W(h0, g, C, j), GOL_W(h1, g, C, j), GOL_W(c, g, B, j), st.mask[j]);
                 nv[j] = valid ? o : 0u;
             }
         }
@@ -507,14 +519,14 @@ __device__ __forceinline__ void bit_phase(BitState<V, K, CL, RING> &S, const Str
     }
 }
 
-template <int V, int K, int CL, int RING, int AUX, bool EDGE, int G, int... P>
+template <int V, int K, int CL, int RING, int AUX, bool EDGE, int G, typename ST, int... P>
 __device__ __forceinline__ void bit_phases(BitState<V, K, CL, RING> &S, const Strip<V> &st, const StencilArgs &a,
-                                           int it, int N, std::integer_sequence<int, P...>) {
-    (bit_phase<V, K, CL, RING, AUX, EDGE, P, G>(S, st, a, it + P, N), ...);
+                                           int it, int N, const ST &stage, std::integer_sequence<int, P...>) {
+    (bit_phase<V, K, CL, RING, AUX, EDGE, P, G, ST>(S, st, a, it + P, N, stage), ...);
 }
 
-template <int V, int K, int CL, int RING, int AUX, bool EDGE, int G>
-__device__ __forceinline__ void bit_run(const Strip<V> &st, const StencilArgs &a) {
+template <int V, int K, int CL, int RING, int AUX, bool EDGE, int G, typename ST = LifeStage>
+__device__ __forceinline__ void bit_run(const Strip<V> &st, const StencilArgs &a, const ST &stage = ST{}) {
     using State = BitState<V, K, CL, RING>;
     State S;
 #pragma unroll
@@ -534,7 +546,7 @@ __device__ __forceinline__ void bit_run(const Strip<V> &st, const StencilArgs &a
     // unrolled by lcm(3, RING) phases so every window and ring slot index is static
     constexpr int U = RING % 3 == 0 ? RING : 3 * RING;
     for (int it = 0; it < N; it += U)   // iterations past N are harmless: no loads, no stores
-        bit_phases<V, K, CL, RING, AUX, EDGE, G>(S, st, a, it, N, std::make_integer_sequence<int, U>{});
+        bit_phases<V, K, CL, RING, AUX, EDGE, G, ST>(S, st, a, it, N, stage, std::make_integer_sequence<int, U>{});
 }
 
 // LDS row ring (the row-pair kernel below): generation-0 rows reach the
@@ -2987,6 +2999,71 @@ hipError_t launch_interleave_rows_shift(const uint32_t *lin, uint32_t *out, int6
                        dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lin, out, pitch_words, r0, nrows, row_words,
                        ncols, shift);
     return hipGetLastError();
+}
+
+// ------------------------------------------------- life-like rules (B/S notation)
+// The rule-generic instantiation of the bit pipeline (gol_set_rule; k = 1..7 on
+// 2-word groups): the same Strip, Sched, hsum, load ring and EDGE split as
+// bit_pipe_kernel, with the stage of gol_rule.h in place of the B3/S23 truth
+// tables.  The rule is a kernel argument of its own; a wave expands the two
+// masks once into the stage's 17 uniform coefficient words (SGPRs).  Emitted
+// behind every other kernel so that none of them moves.
+struct RuleStage {
+    RuleTable T;
+    template <bool EDGE>
+    __device__ __forceinline__ uint32_t apply(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
+                                              uint32_t c1, uint32_t alive, uint32_t mask) const {
+        return rule_bits<EDGE>(T, a0, a1, b0, b1, c0, c1, alive, mask);
+    }
+};
+
+template <int K, int NCH, int RING, int WPE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
+void bit_rule_kernel(StencilArgs a, Sched q, int nstrips, int nblocks, RuleMasks rule) {
+    constexpr int V = 2, G = 2;
+    for_each_item(a, q, nstrips, nblocks, [&](int strip, int r0, int r1) {
+        Strip<V> st;
+        st.setup(a, K, strip, r0, r1, 0u);
+        RuleStage stage;
+        stage.T = rule_table(rule.birth, rule.survive);
+        constexpr int CL = (K + NCH - 1) / NCH;
+        constexpr int M = 2 * K + (K - 1) / CL;   // as bit_pipe_kernel: the chunk's light cone
+        const uint32_t all = st.mask[0] & st.mask[1];
+        const bool full = __builtin_amdgcn_ballot_w64(all != 0xffffffffu) == 0ull;
+        if (full && st.R0 - M >= a.row_lo && st.R1 + M <= a.row_hi) bit_run<V, K, CL, RING, 0, false, G>(st, a, stage);
+        else bit_run<V, K, CL, RING, 0, true, G>(st, a, stage);
+    });
+}
+
+// Rings and chains per depth start from bit_kernel()'s; waves per SIMD: DESIGN.md §3.
+static const void *bit_rule_fn(int gens) {
+    switch (gens) {
+    case 1: return (const void *)&bit_rule_kernel<1, 1, 18, 4>;
+    case 2: return (const void *)&bit_rule_kernel<2, 1, 24, 4>;
+    case 3: return (const void *)&bit_rule_kernel<3, 1, 6, 4>;
+    case 4: return (const void *)&bit_rule_kernel<4, 1, 6, 4>;
+    case 5: return (const void *)&bit_rule_kernel<5, 2, 6, 4>;
+    case 6: return (const void *)&bit_rule_kernel<6, 2, 6, 4>;
+    case 7: return (const void *)&bit_rule_kernel<7, 2, 6, 4>;
+    default: return nullptr;
+    }
+}
+
+bool bit_rule_supported(int gens, int gw) { return gw == 2 && bit_rule_fn(gens) != nullptr; }
+
+hipError_t launch_bit_rule(const StencilArgs &a, int gens, const RuleMasks &rule, hipStream_t s) {
+    if (a.out_r1 <= a.out_r0) return hipSuccess;
+    if (!rule_valid(rule.birth, rule.survive)) return hipErrorInvalidValue;
+    const void *fn = a.gw == 2 ? bit_rule_fn(gens) : nullptr;
+    if (!fn) return hipErrorInvalidValue;   // no fall-back: a depth without a rule kernel is an error
+    int waves = 0, ns = 0;
+    Sched q = plan_items(a, gens, 2, true, fn, waves, ns);
+    if (q.nitems <= 0) return hipSuccess;
+    int nb = (waves + 3) / 4;
+    StencilArgs aa = a;
+    RuleMasks rr = rule;
+    void *args[] = {&aa, &q, &ns, &nb, &rr};
+    return hipLaunchKernel(fn, dim3(nb), dim3(256), args, 0, s);
 }
 
 } // namespace gol

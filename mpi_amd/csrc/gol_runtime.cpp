@@ -227,6 +227,8 @@ struct gol_ctx {
     bool timing = false;
     bool comm_timing = false;    // GOL_OPT_COMM_TIMING
     bool halo_exchange = true;   // GOL_OPT_HALO_EXCHANGE (0: diagnostic, the exchange is skipped)
+    RuleMasks rule{kLifeBirth, kLifeSurvive};   // gol_set_rule (B3/S23: the tuned kernels)
+    bool rule_kernel = false;    // GOL_OPT_RULE_KERNEL: B3/S23 through the rule-generic kernel too
     int64_t text_block_bytes = 64LL << 20;   // snapshot text staging block (GOL_OPT_TEXT_BLOCK_BYTES)
     std::vector<Slab> slabs;     // slabs held by this context
     int cur = 0;                 // parity of the buffer holding the current generation
@@ -370,6 +372,21 @@ int64_t storage_rows(const gol_ctx *c, const Slab &s) { return s.H + 2 * c->hk; 
 // torus, whose single slab is a ring of one.
 bool ring_path(const gol_ctx *c) { return c->nslabs > 1 || c->torus; }
 
+// Life-like rules (gol_set_rule): a launch goes to the rule-generic kernel when
+// the rule is not B3/S23 or GOL_OPT_RULE_KERNEL asks for it.
+bool rule_generic(const gol_ctx *c) {
+    return c->rule_kernel || c->rule.birth != kLifeBirth || c->rule.survive != kLifeSurvive;
+}
+// What keeps this context from the rule-generic kernel (nullptr: nothing).
+const char *rule_limit(const gol_ctx *c) {
+    if (c->layout != GOL_LAYOUT_BIT) return "the byte layout computes B3/S23 only (rules need GOL_LAYOUT_BIT)";
+    if (c->boundary == GOL_SERIAL_COMPAT || c->boundary == GOL_MESH_COMPAT)
+        return "GOL_SERIAL_COMPAT and GOL_MESH_COMPAT reproduce the reference program, which knows B3/S23 only "
+               "(rules need GOL_DEAD or GOL_TORUS)";
+    if (!bit_rule_supported(c->K, c->gw)) return "the rule-generic kernel fuses tblock_k = 1 .. 7 generations (2-word groups)";
+    return nullptr;
+}
+
 int validate(gol_ctx *c, int64_t rows, int64_t cols, int nslabs, int layout, int boundary, int mesh_m,
              int k) {
     if (rows < 1 || cols < 1) return fail(c, GOL_EINVAL, "rows/cols must be positive");
@@ -379,7 +396,7 @@ int validate(gol_ctx *c, int64_t rows, int64_t cols, int nslabs, int layout, int
     if (k < 1 || (k > 8 && !(layout == GOL_LAYOUT_BYTE ? bytebit_supported(k) : bit_depth_supported(k))))
         return fail(c, GOL_EINVAL,
                     "tblock_k must be in [1,8] (bit layout: also 16 or 32; byte layout: also 12, 16, 20, 24, 28, 32, "
-                    "48 or 64)");
+                    "48, 56 or 64)");
     if (nslabs < 1) return fail(c, GOL_EINVAL, "need at least one slab");
     // MESH_COMPAT(m) is main.cpp on an m×m mesh: column block cy's left ghost
     // column holds the LAST column of block cy+1 and its right ghost the FIRST
@@ -615,7 +632,8 @@ int launch_stencil(gol_ctx *c, Slab &s, int gens, int r0, int r1, hipStream_t st
           std::min<int64_t>(s.H + 2 * c->hk, (int64_t)r1 + gens));
     tr_op(c, TR_WRITE, st, nullptr, s.index, c->cur ^ 1, r0, r1);
     if (c->layout == GOL_LAYOUT_BIT) {
-        HIPCHK(c, launch_bit_pipe(a, gens, st));
+        if (rule_generic(c)) HIPCHK(c, launch_bit_rule(a, gens, c->rule, st));
+        else HIPCHK(c, launch_bit_pipe(a, gens, st));
     } else {
         if (c->byte_core && bytebit_supported(gens))
             HIPCHK(c, launch_bytebit_pipe(a, gens, st, c->byte_core));
@@ -1919,11 +1937,79 @@ int gol_set_option(gol_ctx *c, int option, int64_t value) {
         }
         return GOL_OK;
     }
+    case GOL_OPT_RULE_KERNEL: {
+        if (value != 0 && value != 1) return fail(c, GOL_EINVAL, "rule kernel must be 0 or 1");
+        if (value == 1)
+            if (const char *why = rule_limit(c)) return fail(c, GOL_EUNSUPPORTED, "GOL_OPT_RULE_KERNEL: %s", why);
+        if ((value != 0) == c->rule_kernel) return GOL_OK;
+        if (int rc = sync_all(c, nullptr)) return rc;
+        c->rule_kernel = value != 0;
+        return GOL_OK;
+    }
     case GOL_OPT_WORDS_PER_LANE:   // retired in 0.2 (the kernels fix their lane width): accepted, ignored
     case GOL_OPT_SPLIT:            // retired in 0.2 (boundary bands always split off): accepted, ignored
         return GOL_OK;
     default: return fail(c, GOL_EINVAL, "unknown option %d", option);
     }
+}
+
+// "B36/S23" or "S23/B36" (either letter case), or the legacy survive/birth form "23/3".
+int gol_parse_rule(const char *text, uint32_t *birth, uint32_t *survive) {
+    if (!text || !birth || !survive) return GOL_EINVAL;
+    uint32_t m[2] = {0, 0};   // [0] birth, [1] survive
+    bool seen[2] = {false, false};
+    const char *p = text;
+    const bool letters = *p == 'B' || *p == 'b' || *p == 'S' || *p == 's';
+    for (int part = 0; part < 2; ++part) {
+        int which;
+        if (letters) {
+            if (*p == 'B' || *p == 'b') which = 0;
+            else if (*p == 'S' || *p == 's') which = 1;
+            else return GOL_EINVAL;
+            ++p;
+        } else {
+            which = part == 0 ? 1 : 0;
+        }
+        if (seen[which]) return GOL_EINVAL;
+        seen[which] = true;
+        for (; *p >= '0' && *p <= '9'; ++p) {
+            const uint32_t bit = 1u << (*p - '0');
+            if (*p == '9' || (m[which] & bit)) return GOL_EINVAL;   // counts are 0..8, each at most once
+            m[which] |= bit;
+        }
+        if (part == 0) {
+            if (*p != '/') return GOL_EINVAL;
+            ++p;
+        }
+    }
+    if (*p != '\0') return GOL_EINVAL;
+    if (!letters && !m[0] && !m[1]) return GOL_EINVAL;   // a bare "/" names nothing
+    *birth = m[0];
+    *survive = m[1];
+    return GOL_OK;
+}
+
+int gol_set_rule(gol_ctx *c, uint32_t birth, uint32_t survive) {
+    if (!c) return GOL_EINVAL;
+    if ((birth | survive) & ~kRuleBits) return fail(c, GOL_EINVAL, "rule bits above 8 (a cell has 8 neighbours)");
+    if (birth & 1u)
+        return fail(c, GOL_EINVAL, "B0 rules are not supported: the outside of the grid is permanently dead");
+    const bool life = birth == kLifeBirth && survive == kLifeSurvive;
+    if (!life)
+        if (const char *why = rule_limit(c)) return fail(c, GOL_EUNSUPPORTED, "gol_set_rule: %s", why);
+    if (birth == c->rule.birth && survive == c->rule.survive) return GOL_OK;
+    // holds from the next gol_step, which starts from an idle context
+    if (int rc = sync_all(c, nullptr)) return rc;
+    c->rule.birth = birth;
+    c->rule.survive = survive;
+    return GOL_OK;
+}
+
+int gol_get_rule(gol_ctx *c, uint32_t *birth, uint32_t *survive) {
+    if (!c || !birth || !survive) return GOL_EINVAL;
+    *birth = c->rule.birth;
+    *survive = c->rule.survive;
+    return GOL_OK;
 }
 
 int gol_get_option(gol_ctx *c, int option, int64_t *value) {
@@ -1939,6 +2025,7 @@ int gol_get_option(gol_ctx *c, int option, int64_t *value) {
     case GOL_OPT_SCHED_TRACE: *value = c->tracing; return GOL_OK;
     case GOL_OPT_COMM_TIMING: *value = c->comm_timing; return GOL_OK;
     case GOL_OPT_HALO_EXCHANGE: *value = c->halo_exchange; return GOL_OK;
+    case GOL_OPT_RULE_KERNEL: *value = c->rule_kernel; return GOL_OK;
     case GOL_OPT_WORDS_PER_LANE: *value = c->layout == GOL_LAYOUT_BIT ? c->gw : 4; return GOL_OK;
     case GOL_OPT_SPLIT: *value = 1; return GOL_OK;
     default: return fail(c, GOL_EINVAL, "unknown option %d", option);

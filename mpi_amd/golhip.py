@@ -33,6 +33,7 @@ OPT_INTERIOR_SPLIT = 12
 OPT_SCHED_TRACE = 13
 OPT_COMM_TIMING = 14
 OPT_HALO_EXCHANGE = 15
+OPT_RULE_KERNEL = 16
 # retired in 0.2 (accepted by gol_set_option as no-ops; kept so old callers still run)
 OPT_WORDS_PER_LANE = 3
 OPT_SPLIT = 6
@@ -45,7 +46,7 @@ EXPORTS = [
     "gol_download_window", "gol_popcount", "gol_generation", "gol_kernel_time", "gol_last_error",
     "gol_destroy", "gol_version", "gol_text_bytes", "gol_format_text", "gol_write_text", "gol_parse_text",
     "gol_read_text", "gol_download_window_async", "gol_clock_start", "gol_clock_stop", "gol_rccl_selftest",
-    "gol_sched_trace", "gol_comm_time",
+    "gol_sched_trace", "gol_comm_time", "gol_parse_rule", "gol_set_rule", "gol_get_rule",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -105,6 +106,9 @@ def load() -> ctypes.CDLL:
         "gol_clock_start": ([P, ctypes.c_double], i32),
         "gol_clock_stop": ([P, dp, dp], i32),
         "gol_rccl_selftest": ([i32, i64, i32, dp, ctypes.c_char_p, i32], i32),
+        "gol_parse_rule": ([ctypes.c_char_p, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
+        "gol_set_rule": ([P, u32, u32], i32),
+        "gol_get_rule": ([P, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -125,6 +129,16 @@ def slab_plan(rows: int, world: int, rank: int) -> tuple[int, int]:
     if rc:
         raise GolError(rc, "gol_slab_plan")
     return r0.value, n.value
+
+
+def parse_rule(text: str) -> tuple[int, int]:
+    """(birth, survive) masks of a life-like rule: "B36/S23", "S23/B36" (either letter
+    case) or the legacy survive/birth form "23/3".  Bit n = n live neighbours.  Host-only."""
+    b, s = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = load().gol_parse_rule(text.encode(), ctypes.byref(b), ctypes.byref(s))
+    if rc:
+        raise GolError(rc, f"gol_parse_rule: not a B/S rule: {text!r}")
+    return b.value, s.value
 
 
 def unique_id() -> bytes:
@@ -180,7 +194,7 @@ class Engine:
     def __init__(self, rows: int, cols: int, *, n_gpus: int = 1, layout: str = "bit",
                  boundary: str = "dead", mesh_m: int = 1, tblock_k: int = 1,
                  rank: int | None = None, world: int | None = None, device: int = 0,
-                 uid: bytes | None = None):
+                 uid: bytes | None = None, rule: str | tuple[int, int] | None = None):
         self.lib = load()
         self._pending = []   # arrays the library fills at the next synchronising call
         self.rows, self.cols = rows, cols
@@ -199,6 +213,12 @@ class Engine:
             self.rank, self.world = rank, world
         if rc:
             raise GolError(rc, "gol_create failed (see stderr)")
+        if rule is not None:
+            try:
+                self.set_rule(rule)
+            except Exception:
+                self.close()
+                raise
 
     # ------------------------------------------------------------ plumbing
     def _chk(self, rc: int, what: str):
@@ -230,6 +250,20 @@ class Engine:
         v = ctypes.c_int64()
         self._chk(self.lib.gol_get_option(self._c, opt, ctypes.byref(v)), "gol_get_option")
         return v.value
+
+    def set_rule(self, rule: str | tuple[int, int]):
+        """Life-like rule from the next step on: B/S text (parse_rule) or (birth, survive)
+        masks.  Synchronises.  Rules other than B3/S23: bit layout, tblock_k 1..7, dead or
+        torus boundary.  RCCL mode: collective (set it alike on every rank)."""
+        birth, survive = parse_rule(rule) if isinstance(rule, str) else rule
+        self._chk(self.lib.gol_set_rule(self._c, birth, survive), "gol_set_rule")
+
+    @property
+    def rule(self) -> tuple[int, int]:
+        """(birth, survive) masks of the rule in force."""
+        b, s = ctypes.c_uint32(), ctypes.c_uint32()
+        self._chk(self.lib.gol_get_rule(self._c, ctypes.byref(b), ctypes.byref(s)), "gol_get_rule")
+        return b.value, s.value
 
     # ------------------------------------------------------------ board state
     def initialize_board(self, mode: str = "stream", seed: int = 1):
