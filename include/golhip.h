@@ -262,6 +262,39 @@ int gol_read_text(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64
 /* Live cells held by this context (all its slabs). */
 int gol_popcount(gol_ctx *ctx, int64_t *live);
 
+/* Board digest: 128 bits (two 64-bit lanes) of the LOGICAL board, computed where
+ * the board lives — "is this board the same as that one?", "has it started
+ * repeating?" without a download.  All arithmetic mod 2^64:
+ *   sm(x):  z = x + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *           z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)    (splitmix64)
+ *   A_i(r) = sm(4r + i) | 1,  B_i(w) = sm(4w + 2 + i) | 1,  i = 0, 1
+ *   digest[i] = sum over the live cells (r, c) of A_i(r) * B_i(c >> 5) * 2^(c & 31)
+ * with GLOBAL (r, c).  It is the same for every layout, group width, tblock_k,
+ * boundary storage (torus ghost columns, MESH_COMPAT's reversed blocks), slab count
+ * and transport: it equals the digest of what gol_download returns, in every state
+ * (GOL_SERIAL_COMPAT: the inactive last row and column are stored as 0).  The empty
+ * board gives (0, 0); digests of disjoint windows ADD (mod 2^64), so rows this
+ * context does not hold contribute nothing and the parts of rank contexts add up to
+ * the board's digest (no collective is involved; the caller adds).  Two boards that
+ * differ inside one aligned 32-column word of one row always differ in both lanes;
+ * any other difference is caught with probability ~1 - 2^-64 per lane.  Not
+ * cryptographic.  No reference counterpart.
+ *   gol_digest         whole grid; synchronises.
+ *   gol_digest_window  a window; synchronises.  A window outside the grid is GOL_EINVAL.
+ *   gol_digest_async   whole grid, enqueued behind every gol_step so far (no host wait,
+ *                      no device idle); `digest` (caller-owned, valid until then) is
+ *                      filled by the next synchronising call, as the windows of
+ *                      gol_download_window_async are.  At most 1024 may be pending per
+ *                      context: one more is GOL_ESTATE (sync first).  A failed call
+ *                      leaves no pending write.
+ * The digest slots are allocated at the first call of any of the three; while a clock
+ * probe runs nothing is allocated (gol_clock_start), so a context that has taken no
+ * digest yet returns GOL_ESTATE: take one beforehand. */
+int gol_digest(gol_ctx *ctx, uint64_t digest[2]);
+int gol_digest_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
+                      uint64_t digest[2]);
+int gol_digest_async(gol_ctx *ctx, uint64_t digest[2]);
+
 /* Generations advanced so far. */
 int gol_generation(gol_ctx *ctx, int64_t *generation);
 
@@ -296,7 +329,8 @@ int gol_sched_trace(gol_ctx *ctx, int64_t *ops, int64_t cap, int64_t *n);
  * allocated on the device: window copies (gol_download_window[_async],
  * gol_upload_window) use the context's pooled staging (GOL_ESTATE if no pooled
  * buffer of the size is free: copy one window of that size beforehand), and
- * the snapshot-text calls and gol_init_glibc return GOL_ESTATE. */
+ * the snapshot-text calls and gol_init_glibc return GOL_ESTATE; gol_digest* need
+ * their slots allocated by an earlier digest (GOL_ESTATE otherwise). */
 int gol_clock_start(gol_ctx *ctx, double max_ms);
 int gol_clock_stop(gol_ctx *ctx, double *mhz, double *span_ms);
 

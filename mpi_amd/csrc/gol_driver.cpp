@@ -48,6 +48,11 @@
 //                           (loaded into the global scope before any rank;
 //                           tests: tests/shim/libfake_rccl.so)
 //   --same-device           --rccl: every rank on device 0
+//   --digest                print "digest <generation> <32 hex digits>" (gol_digest,
+//                           lane 0 then lane 1) for the starting board, at every
+//                           multiple of the gap (a snapshot point, saving or not) and
+//                           at the end; with --gpus N / --rccl the slabs' parts
+//                           summed.  Without it stdout is unchanged
 #include <dlfcn.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -59,6 +64,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -143,6 +149,7 @@ struct Opts {
     bool rccl = false, same_device = false;
     std::string rccl_lib;
     std::string rule;     // --rule: B/S notation (empty: B3/S23 on the tuned kernels)
+    bool digest = false;  // --digest: print the board's digest at every snapshot point and at the end
 };
 
 // One rank of --rccl: its context and what it reports.
@@ -150,6 +157,7 @@ struct RankRun {
     gol_ctx *ctx = nullptr;
     double dev_ms = 0.0;
     int64_t live = 0, launches = 0;
+    std::vector<std::array<uint64_t, 3>> digests;   // --digest: (generation, lane 0, lane 1) of this context's rows
     std::string err;
 };
 
@@ -188,6 +196,7 @@ int main(int argc, char **argv) {
         else if (a == "--rccl") o.rccl = true;
         else if (a == "--rccl-lib") o.rccl_lib = next();
         else if (a == "--same-device") o.same_device = true;
+        else if (a == "--digest") o.digest = true;
         else pos.push_back(argv[i]);
     }
     long m_rows = 0, m_cols = 0;
@@ -322,7 +331,14 @@ int main(int argc, char **argv) {
     auto run = [&](int i) {
         gol_ctx *ctx = rk[i].ctx;
         double dev_ms = 0.0;
-        if (save) {
+        // --digest: this context's part of the board's digest (gol_digest; the parts add)
+        auto take_digest = [&](int gen) {
+            uint64_t d[2] = {0, 0};
+            check(ctx, gol_digest(ctx, d), "gol_digest");
+            rk[i].digests.push_back({(uint64_t)gen, d[0], d[1]});
+        };
+        if (o.digest) take_digest(from);
+        if (save || (o.digest && gap > 0)) {
             // step straight to the next snapshot (k-generation blocks inside gol_step)
             for (int a = from; a < iters;) {
                 const int next = std::min(iters, (a / gap + 1) * gap);
@@ -332,8 +348,9 @@ int main(int argc, char **argv) {
                     double ms = 0;
                     check(ctx, gol_sync(ctx, &ms), "gol_sync");
                     dev_ms += ms;
-                    for (int p = 0; p < parts; ++p)
+                    for (int p = 0; save && p < parts; ++p)
                         if (!o.rccl || p == i) write_snap(ctx, a, p);
+                    if (o.digest) take_digest(a);
                 }
             }
         } else {
@@ -342,6 +359,7 @@ int main(int argc, char **argv) {
         double ms = 0;
         check(ctx, gol_sync(ctx, &ms), "gol_sync");
         rk[i].dev_ms = dev_ms + ms;
+        if (o.digest && rk[i].digests.back()[0] != (uint64_t)iters) take_digest(iters);
         double kernel_ms = 0;
         check(ctx, gol_popcount(ctx, &rk[i].live), "gol_popcount");
         check(ctx, gol_kernel_time(ctx, &kernel_ms, &rk[i].launches, 0), "gol_kernel_time");
@@ -398,6 +416,16 @@ int main(int argc, char **argv) {
         fprintf(f, "%ld,%ld,%d,%d,%s,%d,%.3f,%.3f,%lld,%lld\n", rows, cols, iters, parts,
                 layout == GOL_LAYOUT_BIT ? "bit" : "byte", o.k, dev_ms, gcups, (long long)live, (long long)launches);
         fclose(f);
+    }
+    // --digest: one line per point, the contexts' parts summed (mod 2^64), lane 0 then lane 1
+    for (size_t j = 0; o.digest && j < rk[0].digests.size(); ++j) {
+        uint64_t d[2] = {0, 0};
+        for (auto &r : rk) {
+            d[0] += r.digests[j][1];
+            d[1] += r.digests[j][2];
+        }
+        printf("digest %llu %016llx%016llx\n", (unsigned long long)rk[0].digests[j][0], (unsigned long long)d[0],
+               (unsigned long long)d[1]);
     }
     printf("0: %s  gens=%d  device %.3f ms  %.1f GCUPS  live=%lld  launches=%lld%s\n", name.c_str(), iters - from,
            dev_ms, gcups, (long long)live, (long long)launches, o.rccl ? "  (rccl ranks)" : "");

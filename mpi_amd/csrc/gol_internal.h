@@ -165,4 +165,14 @@ hipError_t launch_interleave_rows_shift(const uint32_t *lin, uint32_t *out, int6
 hipError_t launch_popcount_cols(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t c0,
                                 int64_t c1, unsigned long long *acc, int bit_gw, hipStream_t s);
 
+// ---- gol_digest*: the layout-independent board digest (gol_digest.h) ----
+// Storage rows [r0, r1) × storage columns [pc0, pc0 + ncols) of a slab buffer,
+// where storage row r0 is GLOBAL row grow0 and storage column pc0 is logical
+// column lc0 (lc0 - pc0 is arbitrary: torus ghost margin, MESH_COMPAT runs, user
+// windows): both lanes of the cells' digest are added into slot[0], slot[1].
+// Exactly these cells are read as cells (partial first and last words are
+// masked).  bit_gw: 0 = byte layout, else the bit layout's group width.
+hipError_t launch_digest(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t grow0, int64_t pc0,
+                         int64_t lc0, int64_t ncols, unsigned long long *slot, int bit_gw, hipStream_t s);
+
 } // namespace gol

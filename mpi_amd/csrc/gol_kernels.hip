@@ -29,6 +29,7 @@
 //  * bit layout, life-like rules other than B3/S23 (k <= 7): bit_rule_kernel, the
 //                 bit pipeline with the table-driven stage of gol_rule.h (end of file).
 #include "gol_internal.h"
+#include "gol_digest.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -3064,6 +3065,121 @@ hipError_t launch_bit_rule(const StencilArgs &a, int gens, const RuleMasks &rule
     RuleMasks rr = rule;
     void *args[] = {&aa, &q, &ns, &nb, &rr};
     return hipLaunchKernel(fn, dim3(nb), dim3(256), args, 0, s);
+}
+
+// ------------------------------------------------------------------------ digest
+// gol_digest* (gol_digest.h): a streaming, read-only reduction of a window of
+// storage rows × storage columns.  A wave takes items of 64 units along the row
+// (a lane = one unit: 16 B of a bit row, 32 B of a byte row, so a wave's load
+// is one contiguous 1- or 2-KiB run) times a segment of 64·m rows.  Per item a
+// lane computes its window masks and its NL + 1 weights B_i(w) once and keeps
+// them down the rows; per block of 64 rows lane j computes A_i of row j, handed
+// to the wave through v_readlane as the rows are walked, so a row costs the
+// de-interleave (10 word-pair exchanges), one funnel shift and 2·(NL + 1)
+// 64×32 multiply-adds per lane, plus one 64×64 multiply per lane and hash lane
+// for A_i(r).  Lanes past the last unit read the first unit under a zero mask.
+// At the end one wave reduction (__shfl_down) and one 64-bit vector atomicAdd
+// per hash lane and wave: integer addition commutes, so the result does not
+// depend on the arrival order.  Templates on G (0 = byte), emitted behind every
+// other kernel so that none of them moves.
+__device__ __forceinline__ uint64_t digest_readlane(uint64_t v, int j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void digest_kernel(const uint8_t *__restrict__ buf, int64_t pitch_bytes, int64_t r0,
+                                                     int64_t nrows, int64_t grow0, int64_t pc0, int64_t lc0,
+                                                     int64_t ncols, int seg_rows, int64_t q0, int64_t nunits,
+                                                     unsigned long long *slot) {
+    typedef DigestUnit<G> U;
+    constexpr int NL = U::NL;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const int64_t ncb = (nunits + 63) / 64, nseg = (nrows + seg_rows - 1) / seg_rows;
+    const DigestShift h = digest_shift_of(pc0, lc0);
+    uint64_t acc[2] = {0, 0};
+    for (int64_t item = wave; item < ncb * nseg; item += nwaves) {
+        const int64_t seg = item / ncb, cb = item % ncb;
+        const bool on = cb * 64 + lane < nunits;
+        const int64_t q = on ? q0 + cb * 64 + lane : q0;
+        uint32_t mask[NL];
+        uint64_t Bu[2][5];
+#pragma unroll
+        for (int t = 0; t < NL; ++t) mask[t] = on ? digest_mask(NL * q + t, pc0, pc0 + ncols) : 0u;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int t = 0; t <= NL; ++t) Bu[i][t] = digest_B(i, NL * q + h.dq + t);
+        const int64_t ra = seg * seg_rows, rb = ra + seg_rows < nrows ? ra + seg_rows : nrows;
+        for (int64_t rs = ra; rs < rb; rs += 64) {
+            const uint64_t a0 = digest_A(0, grow0 + rs + lane), a1 = digest_A(1, grow0 + rs + lane);
+            const int n = rb - rs < 64 ? (int)(rb - rs) : 64;
+            const uint8_t *p = buf + (r0 + rs) * pitch_bytes + q * U::BYTES;
+            // four rows' loads are issued before the first is used (one load in flight per wave
+            // left the kernel latency-bound at 3 TB/s); a row past the block's last is the last
+            // row again under a zero A
+            for (int j0 = 0; j0 < n; j0 += 4) {
+                uint4 x[4][U::WORDS / 4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int j = j0 + u < n ? j0 + u : n - 1;
+#pragma unroll
+                    for (int v = 0; v < U::WORDS / 4; ++v)
+                        x[u][v] = reinterpret_cast<const uint4 *>(p + j * pitch_bytes)[v];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    uint32_t w[U::WORDS];
+#pragma unroll
+                    for (int v = 0; v < U::WORDS / 4; ++v) {
+                        w[4 * v] = x[u][v].x;
+                        w[4 * v + 1] = x[u][v].y;
+                        w[4 * v + 2] = x[u][v].z;
+                        w[4 * v + 3] = x[u][v].w;
+                    }
+                    uint64_t sum[2] = {0, 0};
+                    digest_unit<G>(w, mask, h.s, Bu, sum);
+                    const bool live = j0 + u < n;   // (wave-uniform)
+                    acc[0] += (live ? digest_readlane(a0, j0 + u) : 0ull) * sum[0];
+                    acc[1] += (live ? digest_readlane(a1, j0 + u) : 0ull) * sum[1];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        unsigned long long v = acc[i];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0 && v) atomicAdd(slot + i, v);
+    }
+}
+
+hipError_t launch_digest(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t grow0, int64_t pc0,
+                         int64_t lc0, int64_t ncols, unsigned long long *slot, int bit_gw, hipStream_t s) {
+    const int64_t nrows = r1 - r0;
+    if (nrows <= 0 || ncols <= 0) return hipSuccess;
+    if (r0 < 0 || pc0 < 0 || lc0 < 0 || grow0 < 0 || (bit_gw != 0 && bit_gw != 2 && bit_gw != 4))
+        return hipErrorInvalidValue;
+    const int64_t ucols = bit_gw ? DigestUnit<2>::COLS : DigestUnit<0>::COLS;
+    const int64_t q0 = pc0 / ucols, nunits = (pc0 + ncols - 1) / ucols - q0 + 1;
+    const int64_t ncb = (nunits + 63) / 64;
+    // segments of 64·m rows: as many items as the capped grid has waves where the window
+    // allows (the grid is capped as launch_popcount's), longer segments beyond that, so
+    // a lane's weights serve up to 512 rows
+    constexpr int64_t kMaxBlocks = 4096;
+    int64_t m = (nrows + 63) / 64 * ncb / (kMaxBlocks * 4);
+    m = m < 1 ? 1 : m > 8 ? 8 : m;
+    int seg_rows = (int)(64 * m);
+    const int64_t items = ncb * ((nrows + seg_rows - 1) / seg_rows);
+    int64_t blocks = (items + 3) / 4;
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    const auto fn = bit_gw == 4 ? digest_kernel<4> : bit_gw == 2 ? digest_kernel<2> : digest_kernel<0>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const uint8_t *>(buf), pitch_bytes, r0,
+                       nrows, grow0, pc0, lc0, ncols, seg_rows, q0, nunits, slot);
+    return hipGetLastError();
 }
 
 } // namespace gol

@@ -110,6 +110,9 @@ struct Slab {
     int row_lo = 0, row_hi = 0; // storage rows outside are dead
     void *buf[2] = {nullptr, nullptr};
     unsigned long long *d_count = nullptr;
+    // gol_digest*: a ring of kDigestRing 16-byte slots (two lanes each), device and
+    // pinned host mirror, allocated at first use
+    unsigned long long *dg_dev = nullptr, *dg_host = nullptr;
     hipStream_t comp = nullptr, comm = nullptr;
     // GOL_OPT_INTERIOR_SPLIT = P >= 2: interior parts 1 .. P-1 run on streams of their own
     // (part 0 on comp); nx = how many such streams exist (created on first use)
@@ -152,6 +155,13 @@ struct PendingWindow {
     uint8_t *host = nullptr;   // caller's rows, leading dimension ld
     int64_t ld = 0, nrows = 0, ncols = 0;
 };
+
+// A digest enqueued by gol_digest_async: pending digest j owns slot j of every
+// slab's ring; sync_all sums the slabs' mirrors into the caller's two words.
+struct PendingDigest {
+    uint64_t *out = nullptr;
+};
+constexpr size_t kDigestRing = 1024;   // digests pending per context at most
 
 // The schedule trial of the k=8 bit kernel (see tune_slot).
 // (2-word groups: six rounds are the default; 4-word groups: guided, 4 rounds;
@@ -259,6 +269,7 @@ struct gol_ctx {
     std::vector<PendingWindow> pending;
     std::vector<Staging> staging;
     std::vector<size_t> release_at_sync;   // staging of a failed async copy: busy until the next sync
+    std::vector<PendingDigest> pending_digests;   // gol_digest_async (slot = index)
     // clock probe (gol_clock_start / gol_clock_stop)
     hipStream_t clk_stream = nullptr;
     unsigned long long *clk_out = nullptr;   // device: memtime0, realtime0, memtime1, realtime1
@@ -511,6 +522,8 @@ void free_slab(Slab &s) {
         if (s.ev_exch[i]) (void)hipEventDestroy(s.ev_exch[i]);
     }
     if (s.d_count) (void)hipFree(s.d_count);
+    if (s.dg_dev) (void)hipFree(s.dg_dev);
+    if (s.dg_host) (void)hipHostFree(s.dg_host);
     if (s.ev_start) (void)hipEventDestroy(s.ev_start);
     if (s.ev_stop) (void)hipEventDestroy(s.ev_stop);
     for (auto &q : s.comm_ev)
@@ -1149,6 +1162,15 @@ int sync_all(gol_ctx *c, double *elapsed_ms) {
         for (int64_t r = 0; r < w.nrows; ++r) memcpy(w.host + r * w.ld, b.pinned + r * w.ncols, (size_t)w.ncols);
         b.busy = false;
     }
+    // digests enqueued by gol_digest_async: the slabs' parts add (mod 2^64)
+    std::vector<PendingDigest> dg;
+    dg.swap(c->pending_digests);
+    for (size_t j = 0; j < dg.size(); ++j)
+        for (int i = 0; i < 2; ++i) {
+            uint64_t v = 0;
+            for (auto &s : c->slabs) v += s.dg_host[2 * j + i];
+            dg[j].out[i] = v;
+        }
     if (elapsed_ms) *elapsed_ms = ms_max;
     return GOL_OK;
 }
@@ -1292,6 +1314,96 @@ int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t 
         w.ncols = ncols;
         c->pending.push_back(w);
     }
+    return GOL_OK;
+}
+
+// ----------------------------------------------------------------------- digest
+
+// Enqueue the digest (gol_digest.h) of the window as it stands after every step
+// enqueued so far: per slab, on its compute stream behind the joins window_async
+// makes, the slab's slot is cleared, one launch per storage-contiguous column run
+// adds the cells of the window this slab holds (exact ranges: no pad column,
+// ghost column or halo row is read as a cell), and the slot goes to its pinned
+// mirror; sync_all sums the slabs into `out`.  Rows this context does not hold
+// contribute nothing.  `out` is registered only once every slab is enqueued: a
+// failed call leaves no pending write (its slot is cleared again by the next call).
+int digest_enqueue(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint64_t *out) {
+    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
+        return fail(c, GOL_EINVAL, "window outside the grid");
+    const size_t slot = c->pending_digests.size();
+    if (slot >= kDigestRing)
+        return fail(c, GOL_ESTATE, "%zu digests are pending: sync first", kDigestRing);
+    for (auto &s : c->slabs) {
+        if (s.dg_dev) continue;
+        // an allocation can wait for the whole device, i.e. for a running probe (acquire_staging)
+        if (c->clk_running)
+            return fail(c, GOL_ESTATE, "the digest slots are allocated at first use, which would wait for the "
+                                       "running clock probe: take one digest before gol_clock_start");
+        HIPCHK(c, hipSetDevice(s.device));
+        HIPCHK(c, hipMalloc(&s.dg_dev, kDigestRing * 2 * sizeof(unsigned long long)));
+        if (hipHostMalloc(&s.dg_host, kDigestRing * 2 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
+            (void)hipFree(s.dg_dev);
+            s.dg_dev = nullptr;
+            s.dg_host = nullptr;
+            return fail(c, GOL_ENOMEM, "pinned digest slots");
+        }
+    }
+    const int gw = c->layout == GOL_LAYOUT_BIT ? c->gw : 0;
+    for (auto &s : c->slabs) {
+        HIPCHK(c, hipSetDevice(s.device));
+        unsigned long long *d = s.dg_dev + 2 * slot;
+        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
+        if (r1 <= r0 || ncols == 0) {   // nothing of the window here: the slab's part is (0, 0)
+            HIPCHK(c, hipMemsetAsync(d, 0, 2 * sizeof *d, s.comp));
+            HIPCHK(c, hipMemcpyAsync(s.dg_host + 2 * slot, d, 2 * sizeof *d, hipMemcpyDeviceToHost, s.comp));
+            continue;
+        }
+        // the last step's boundary bands run on the comm stream: join it
+        hipEvent_t e;
+        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        const hipError_t e1 = tr_record(c, e, s.comm);
+        const hipError_t e2 = e1 == hipSuccess ? tr_wait(c, s.comp, e) : e1;
+        (void)hipEventDestroy(e);
+        HIPCHK(c, e2);
+        if (int rc = join_parts(c, s, s.comp)) return rc;   // (a split interior's other parts)
+        const int64_t srow = c->hk + (r0 - s.row0);
+        tr_op(c, TR_READ, s.comp, nullptr, s.index, c->cur, srow, srow + (r1 - r0));
+        HIPCHK(c, hipMemsetAsync(d, 0, 2 * sizeof *d, s.comp));
+        int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
+            HIPCHK(c, launch_digest(s.buf[c->cur], c->pitch_bytes, srow, srow + (r1 - r0), r0, pc, lc, n, d, gw, s.comp));
+            return GOL_OK;
+        });
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(s.dg_host + 2 * slot, d, 2 * sizeof *d, hipMemcpyDeviceToHost, s.comp));
+        // as window_async: the slab's other streams wait for the read before a later
+        // step (the step after next) overwrites this buffer
+        if (s.nx || s.comm != s.comp) {
+            hipEvent_t f;
+            HIPCHK(c, hipEventCreateWithFlags(&f, hipEventDisableTiming));
+            hipError_t f1 = tr_record(c, f, s.comp);
+            if (f1 == hipSuccess && s.comm != s.comp) f1 = tr_wait(c, s.comm, f);
+            for (int j = 0; j < s.nx && f1 == hipSuccess; ++j) f1 = tr_wait(c, s.part[j], f);
+            (void)hipEventDestroy(f);
+            HIPCHK(c, f1);
+        }
+    }
+    PendingDigest p;
+    p.out = out;
+    c->pending_digests.push_back(p);
+    return GOL_OK;
+}
+
+// The synchronising forms: everything pending is delivered first, so slot 0 is free.
+int digest_now(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint64_t digest[2]) {
+    if (int rc = sync_all(c, nullptr)) return rc;
+    uint64_t v[2] = {0, 0};
+    if (int rc = digest_enqueue(c, row0, col0, nrows, ncols, v)) return rc;
+    if (int rc = sync_all(c, nullptr)) {
+        c->pending_digests.clear();   // v leaves scope
+        return rc;
+    }
+    digest[0] = v[0];
+    digest[1] = v[1];
     return GOL_OK;
 }
 
@@ -2244,6 +2356,21 @@ int gol_download_window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nr
                               int64_t ld) {
     if (!c || !host) return GOL_EINVAL;
     return window_async(c, row0, col0, nrows, ncols, host, ld);
+}
+
+int gol_digest(gol_ctx *c, uint64_t digest[2]) {
+    if (!c || !digest) return GOL_EINVAL;
+    return digest_now(c, 0, 0, c->rows, c->cols, digest);
+}
+
+int gol_digest_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint64_t digest[2]) {
+    if (!c || !digest) return GOL_EINVAL;
+    return digest_now(c, row0, col0, nrows, ncols, digest);
+}
+
+int gol_digest_async(gol_ctx *c, uint64_t digest[2]) {
+    if (!c || !digest) return GOL_EINVAL;
+    return digest_enqueue(c, 0, 0, c->rows, c->cols, digest);
 }
 
 // The probe's stream: ONE per device for the whole process (never destroyed).

@@ -47,6 +47,7 @@ EXPORTS = [
     "gol_destroy", "gol_version", "gol_text_bytes", "gol_format_text", "gol_write_text", "gol_parse_text",
     "gol_read_text", "gol_download_window_async", "gol_clock_start", "gol_clock_stop", "gol_rccl_selftest",
     "gol_sched_trace", "gol_comm_time", "gol_parse_rule", "gol_set_rule", "gol_get_rule",
+    "gol_digest", "gol_digest_window", "gol_digest_async",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -109,6 +110,9 @@ def load() -> ctypes.CDLL:
         "gol_parse_rule": ([ctypes.c_char_p, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
         "gol_set_rule": ([P, u32, u32], i32),
         "gol_get_rule": ([P, ctypes.POINTER(u32), ctypes.POINTER(u32)], i32),
+        "gol_digest": ([P, ctypes.POINTER(ctypes.c_uint64)], i32),
+        "gol_digest_window": ([P, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_uint64)], i32),
+        "gol_digest_async": ([P, ctypes.POINTER(ctypes.c_uint64)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -300,6 +304,67 @@ class Engine:
                   "gol_download_window_async")
         self._pending.append(out)   # kept alive here until a synchronising call has filled it
         return out
+
+    # ------------------------------------------------------------ digest
+    def digest(self) -> tuple[int, int]:
+        """128-bit digest of the logical board (two 64-bit lanes), computed on the device:
+        equal for every layout, tblock_k, boundary storage, slab count and transport, and
+        equal to the digest of download() (tests/digest_ref.py).  Rank contexts return
+        their slab's part; the parts add mod 2^64.  Synchronises."""
+        d = (ctypes.c_uint64 * 2)()
+        self._chk(self.lib.gol_digest(self._c, d), "gol_digest")
+        self._pending = []
+        return int(d[0]), int(d[1])
+
+    def digest_window(self, row0: int, col0: int, nrows: int, ncols: int) -> tuple[int, int]:
+        """Digest of a window (global coordinates; digests of disjoint windows add mod
+        2^64).  Rows this context does not hold contribute nothing.  Synchronises."""
+        d = (ctypes.c_uint64 * 2)()
+        self._chk(self.lib.gol_digest_window(self._c, row0, col0, nrows, ncols, d), "gol_digest_window")
+        self._pending = []
+        return int(d[0]), int(d[1])
+
+    def digest_async(self) -> np.ndarray:
+        """Enqueue a whole-board digest behind the steps enqueued so far; the returned
+        array of 2 uint64 is filled by the next synchronising call.  At most 1024 pending
+        (GolError ESTATE beyond: sync first)."""
+        out = np.zeros(2, np.uint64)
+        self._chk(self.lib.gol_digest_async(self._c, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))),
+                  "gol_digest_async")
+        self._pending.append(out)   # kept alive here until a synchronising call has filled it
+        return out
+
+    def find_repeat(self, max_generations: int, every: int | None = None, batch: int = 64):
+        """Step until the board's digest repeats: `every` generations at a time (default
+        tblock_k), a digest_async after each, one sync per `batch` checks — the engine
+        never drains between checks; the comparison is host-side bookkeeping.  Returns
+        (generation_first_seen, generation_repeated) for the first digest seen before
+        (the digest of the current generation is included), or None once max_generations
+        more generations have been stepped (whole multiples of `every`).
+        The distance is a multiple of `every`, and the board's true period divides it;
+        generation_first_seen is the first CHECKED generation inside the cycle.  The
+        engine is left at the end of the batch in which the repeat was found (see
+        `generation`), not at generation_repeated.  A rank context compares its own slab
+        only: a board-wide conclusion needs every rank's answer (or the summed parts)."""
+        every = self.tblock_k if every is None else every
+        if every < 1 or batch < 1 or batch > 1024:
+            raise ValueError("find_repeat: every >= 1 and 1 <= batch <= 1024")
+        seen = {self.digest(): self.generation}
+        gen, left = self.generation, max_generations // every
+        while left > 0:
+            outs = []
+            for _ in range(min(batch, left)):
+                self.step(every)
+                gen += every
+                outs.append((gen, self.digest_async()))
+            left -= len(outs)
+            self.sync()
+            for g, o in outs:
+                key = (int(o[0]), int(o[1]))
+                if key in seen:
+                    return seen[key], g
+                seen[key] = g
+        return None
 
     def clock_start(self, max_ms: float):
         """Start the clock probe (one wave on its own stream, stops by itself after max_ms)."""
