@@ -295,6 +295,47 @@ int gol_digest_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, i
                       uint64_t digest[2]);
 int gol_digest_async(gol_ctx *ctx, uint64_t digest[2]);
 
+/* Density map: per-tile live-cell counts of the LOGICAL board, computed where the
+ * board lives — a coarse view of a board nobody can download (where the live cells
+ * are, where a soup has died out or grows).  The window [row0, row0 + nrows) ×
+ * [col0, col0 + ncols) is cut into tiles of tile_rows × tile_cols cells from its
+ * origin: *trows = ceil(nrows / tile_rows), *tcols = ceil(ncols / tile_cols)
+ * (gol_density_dims: host only, no context; GOL_EINVAL for null pointers, a negative
+ * size or a tile size < 1).
+ *   counts[i*ld + j] = the number of live cells (r, c) with
+ *       row0 + i*tile_rows <= r < min(row0 + (i+1)*tile_rows, row0 + nrows)
+ *       col0 + j*tile_cols <= c < min(col0 + (j+1)*tile_cols, col0 + ncols)
+ * with GLOBAL (r, c); `ld` is in elements and must be >= tcols.  Tiles of the last
+ * tile row and tile column are clipped to the window.  The map equals the map of
+ * what gol_download returns, in every state, for every layout, group width,
+ * tblock_k, boundary storage, slab count and transport: torus ghost columns and
+ * halo rows are never counted, MESH_COMPAT maps are in logical columns, and
+ * GOL_SERIAL_COMPAT's inactive last row and column count 0.  Maps ADD: rows this
+ * context does not hold contribute 0 to every tile, the whole trows × tcols block of
+ * `counts` is always written, and the maps of rank contexts add up to the board's
+ * map (no collective is involved; the caller adds).
+ * GOL_EINVAL (message in gol_last_error): a window outside the grid, tile_rows < 1,
+ * tile_cols < 32 or not a multiple of 32, col0 not a multiple of 32,
+ * tile_rows*tile_cols > 2^32 - 1 (a count is 32 bits), ld < tcols, null pointers.
+ * The multiple-of-32 rule is deliberate in this version: every aligned 32-column
+ * word of a row then belongs to exactly one tile.  An empty window (nrows == 0 or
+ * ncols == 0) is GOL_OK and writes nothing.
+ *   gol_density         whole grid; synchronises.
+ *   gol_density_window  a window; synchronises.
+ *   gol_density_async   whole grid, enqueued behind every gol_step so far (no host
+ *                       wait, no device idle); `counts` (caller-owned, valid until
+ *                       then) is filled by the next synchronising call, as the windows
+ *                       of gol_download_window_async are.  A failed call leaves no
+ *                       pending write.
+ * The per-slab parts live in the context's pooled staging, as window copies do (see
+ * gol_clock_start).  No reference counterpart. */
+int gol_density_dims(int64_t nrows, int64_t ncols, int64_t tile_rows, int64_t tile_cols,
+                     int64_t *trows, int64_t *tcols);
+int gol_density(gol_ctx *ctx, int64_t tile_rows, int64_t tile_cols, uint32_t *counts, int64_t ld);
+int gol_density_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
+                       int64_t tile_rows, int64_t tile_cols, uint32_t *counts, int64_t ld);
+int gol_density_async(gol_ctx *ctx, int64_t tile_rows, int64_t tile_cols, uint32_t *counts, int64_t ld);
+
 /* Generations advanced so far. */
 int gol_generation(gol_ctx *ctx, int64_t *generation);
 
@@ -328,7 +369,9 @@ int gol_sched_trace(gol_ctx *ctx, int64_t *ops, int64_t cap, int64_t *n);
  * probe itself holds one wave slot of one CU).  While it runs nothing is
  * allocated on the device: window copies (gol_download_window[_async],
  * gol_upload_window) use the context's pooled staging (GOL_ESTATE if no pooled
- * buffer of the size is free: copy one window of that size beforehand), and
+ * buffer of the size is free: copy one window of that size beforehand; the
+ * parts of gol_density* come from the same pool under the same rule: take one
+ * map with the same window and tiles beforehand), and
  * the snapshot-text calls and gol_init_glibc return GOL_ESTATE; gol_digest* need
  * their slots allocated by an earlier digest (GOL_ESTATE otherwise). */
 int gol_clock_start(gol_ctx *ctx, double max_ms);

@@ -53,6 +53,17 @@
 //                           multiple of the gap (a snapshot point, saving or not) and
 //                           at the end; with --gpus N / --rccl the slabs' parts
 //                           summed.  Without it stdout is unchanged
+//   --density T[xU]         write the board's density map (gol_density: live cells per
+//                           tile of T rows × U columns; U a multiple of 32, default T)
+//                           as `<name>_<iter>.pgm` at every multiple of the gap (a
+//                           snapshot point, saving or not) and at the end, and print
+//                           "density <generation> <file>".  Binary PGM:
+//                           "P5\n<tcols> <trows>\n65535\n", then 16-bit big-endian
+//                           samples floor(65535 · count / cells), cells = the clipped
+//                           tile's own cell count (edge tiles are not darker).  The map
+//                           is enqueued (gol_density_async) ahead of the point's
+//                           synchronising call: the run is not drained for it; with
+//                           --gpus N / --rccl the contexts' maps are added
 #include <dlfcn.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -71,6 +82,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/golhip.h"
@@ -150,6 +162,7 @@ struct Opts {
     std::string rccl_lib;
     std::string rule;     // --rule: B/S notation (empty: B3/S23 on the tuned kernels)
     bool digest = false;  // --digest: print the board's digest at every snapshot point and at the end
+    int64_t tile_rows = 0, tile_cols = 0;   // --density T[xU] (0: no map)
 };
 
 // One rank of --rccl: its context and what it reports.
@@ -158,8 +171,30 @@ struct RankRun {
     double dev_ms = 0.0;
     int64_t live = 0, launches = 0;
     std::vector<std::array<uint64_t, 3>> digests;   // --digest: (generation, lane 0, lane 1) of this context's rows
+    // --density: (generation, this context's map) per point; a map is filled by the next synchronising call
+    std::vector<std::pair<int, std::vector<uint32_t>>> maps;
     std::string err;
 };
+
+// --density: binary PGM of a map, 16-bit big-endian samples floor(65535 · count / cells of the clipped tile)
+void write_pgm(const std::string &path, const std::vector<uint32_t> &map, int64_t trows, int64_t tcols, long rows,
+               long cols, int64_t tile_rows, int64_t tile_cols) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) die(("cannot create " + path).c_str());
+    fprintf(f, "P5\n%lld %lld\n65535\n", (long long)tcols, (long long)trows);
+    std::vector<uint8_t> line(2 * (size_t)tcols);
+    for (int64_t i = 0; i < trows; ++i) {
+        const uint64_t h = (uint64_t)std::min<int64_t>(tile_rows, rows - i * tile_rows);
+        for (int64_t j = 0; j < tcols; ++j) {
+            const uint64_t cells = h * (uint64_t)std::min<int64_t>(tile_cols, cols - j * tile_cols);
+            const uint64_t v = 65535ull * map[(size_t)(i * tcols + j)] / cells;
+            line[2 * j] = (uint8_t)(v >> 8);
+            line[2 * j + 1] = (uint8_t)v;
+        }
+        if (fwrite(line.data(), 1, line.size(), f) != line.size()) die(("cannot write " + path).c_str());
+    }
+    fclose(f);
+}
 
 // Runs fn(r) for r = 0..n-1 on n host threads at once (the rank calls are
 // collective: every rank must be inside gol_create_rank / gol_step together).
@@ -197,6 +232,21 @@ int main(int argc, char **argv) {
         else if (a == "--rccl-lib") o.rccl_lib = next();
         else if (a == "--same-device") o.same_device = true;
         else if (a == "--digest") o.digest = true;
+        else if (a == "--density") {
+            const char *v = next();
+            char *end = nullptr;
+            o.tile_rows = strtoll(v, &end, 10);
+            o.tile_cols = o.tile_rows;
+            if (end != v && *end == 'x') {
+                const char *u = end + 1;
+                o.tile_cols = strtoll(u, &end, 10);
+                if (end == u) o.tile_rows = 0;
+            }
+            if (end == v || *end || o.tile_rows < 1 || o.tile_cols < 32 || o.tile_cols % 32 ||
+                o.tile_rows > 0xffffffffll / o.tile_cols)
+                die("--density must be T or TxU: tile rows, then tile columns (a multiple of 32, default T), "
+                    "at most 2^32 - 1 cells per tile");
+        }
         else pos.push_back(argv[i]);
     }
     long m_rows = 0, m_cols = 0;
@@ -338,13 +388,24 @@ int main(int argc, char **argv) {
             rk[i].digests.push_back({(uint64_t)gen, d[0], d[1]});
         };
         if (o.digest) take_digest(from);
-        if (save || (o.digest && gap > 0)) {
+        // --density: this context's map (gol_density_async: enqueued here, filled by the next
+        // synchronising call; the contexts' maps add)
+        const bool density = o.tile_rows > 0;
+        auto take_density = [&](int gen) {
+            int64_t tr = 0, tc = 0;
+            check(ctx, gol_density_dims(rows, cols, o.tile_rows, o.tile_cols, &tr, &tc), "gol_density_dims");
+            rk[i].maps.emplace_back(gen, std::vector<uint32_t>((size_t)(tr * tc)));
+            check(ctx, gol_density_async(ctx, o.tile_rows, o.tile_cols, rk[i].maps.back().second.data(), tc),
+                  "gol_density_async");
+        };
+        if (save || ((o.digest || density) && gap > 0)) {
             // step straight to the next snapshot (k-generation blocks inside gol_step)
             for (int a = from; a < iters;) {
                 const int next = std::min(iters, (a / gap + 1) * gap);
                 check(ctx, gol_step(ctx, next - a), "gol_step");
                 a = next;
                 if (a % gap == 0) {
+                    if (density) take_density(a);
                     double ms = 0;
                     check(ctx, gol_sync(ctx, &ms), "gol_sync");
                     dev_ms += ms;
@@ -356,6 +417,7 @@ int main(int argc, char **argv) {
         } else {
             check(ctx, gol_step(ctx, iters - from), "gol_step");
         }
+        if (density && (rk[i].maps.empty() || rk[i].maps.back().first != iters)) take_density(iters);
         double ms = 0;
         check(ctx, gol_sync(ctx, &ms), "gol_sync");
         rk[i].dev_ms = dev_ms + ms;
@@ -426,6 +488,17 @@ int main(int argc, char **argv) {
         }
         printf("digest %llu %016llx%016llx\n", (unsigned long long)rk[0].digests[j][0], (unsigned long long)d[0],
                (unsigned long long)d[1]);
+    }
+    // --density: one PGM per point, the contexts' maps added
+    for (size_t j = 0; j < rk[0].maps.size(); ++j) {
+        std::vector<uint32_t> map = rk[0].maps[j].second;
+        for (size_t r = 1; r < rk.size(); ++r)
+            for (size_t t = 0; t < map.size(); ++t) map[t] += rk[r].maps[j].second[t];
+        int64_t tr = 0, tc = 0;
+        gol_density_dims(rows, cols, o.tile_rows, o.tile_cols, &tr, &tc);
+        const std::string path = name + "_" + std::to_string(rk[0].maps[j].first) + ".pgm";
+        write_pgm(path, map, tr, tc, rows, cols, o.tile_rows, o.tile_cols);
+        printf("density %d %s\n", rk[0].maps[j].first, path.c_str());
     }
     printf("0: %s  gens=%d  device %.3f ms  %.1f GCUPS  live=%lld  launches=%lld%s\n", name.c_str(), iters - from,
            dev_ms, gcups, (long long)live, (long long)launches, o.rccl ? "  (rccl ranks)" : "");

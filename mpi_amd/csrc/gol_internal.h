@@ -175,4 +175,17 @@ hipError_t launch_popcount_cols(const void *buf, int64_t pitch_bytes, int64_t r0
 hipError_t launch_digest(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t grow0, int64_t pc0,
                          int64_t lc0, int64_t ncols, unsigned long long *slot, int bit_gw, hipStream_t s);
 
+// ---- gol_density*: per-tile live-cell counts (gol_density.h) ----
+// The same cells as launch_digest's: storage rows [r0, r1) × storage columns
+// [pc0, pc0 + ncols), storage column pc0 being logical column lc0.  The window the
+// tiles belong to starts at logical column col0 (a multiple of 32, <= lc0) and
+// trow_off rows above storage row r0 (>= 0); tiles are tile_rows × tile_cols
+// (tile_cols a multiple of 32).  The cell of tile (i, j) is counted into
+// part[(i - ti_base) * tcols + j]; the part holds ntr tile rows of tcols counts and
+// is only added to (the caller clears it).  A run that would touch a tile outside
+// the part is hipErrorInvalidValue.
+hipError_t launch_density(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t trow_off, int64_t pc0,
+                          int64_t lc0, int64_t ncols, int64_t col0, int64_t tile_rows, int64_t tile_cols,
+                          uint32_t *part, int64_t ti_base, int64_t ntr, int64_t tcols, int bit_gw, hipStream_t s);
+
 } // namespace gol

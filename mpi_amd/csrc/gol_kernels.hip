@@ -30,6 +30,7 @@
 //                 bit pipeline with the table-driven stage of gol_rule.h (end of file).
 #include "gol_internal.h"
 #include "gol_digest.h"
+#include "gol_density.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -3179,6 +3180,158 @@ hipError_t launch_digest(const void *buf, int64_t pitch_bytes, int64_t r0, int64
     const auto fn = bit_gw == 4 ? digest_kernel<4> : bit_gw == 2 ? digest_kernel<2> : digest_kernel<0>;
     hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const uint8_t *>(buf), pitch_bytes, r0,
                        nrows, grow0, pc0, lc0, ncols, seg_rows, q0, nunits, slot);
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------- density
+// gol_density* (gol_density.h): per-tile live-cell counts, the digest kernel's
+// streaming shape with a popcount where the digest has a weighted sum.  A wave
+// takes items of 64 units along the row (a lane = one unit) times a segment of
+// rows; per item a lane computes its window masks and the tile columns of its
+// NL + 1 canonical words once and keeps them down the rows; four rows' loads are
+// in flight.  A lane adds NL + 1 32-bit counts down the rows of ONE tile row; at a
+// tile-row boundary and at the end of the segment they go to the slab's part:
+// where every lane's words lie in one tile column (wave-uniform test) the lanes
+// that share a tile are first added up by a segmented __shfl_down reduction (tile
+// columns ascend with the lane, so a tile's lanes are neighbours) and the first
+// lane of each tile issues one 32-bit vector atomicAdd; else a lane folds its own
+// neighbouring words and adds per tile column.  Integer addition commutes, so the
+// result does not depend on the arrival order.  Where the run is unshifted and
+// every unit of the wave is whole and inside one tile (wave-uniform), rows are
+// counted on the storage words as they are (density_unit_whole: no
+// de-interleave).  Lanes past the last unit read the first unit and count
+// nothing.  Templates on G (0 = byte), emitted behind every other kernel so that
+// none of them moves.
+template <int G>
+__global__ __launch_bounds__(256) void density_kernel(const uint8_t *__restrict__ buf, int64_t pitch_bytes, int64_t r0,
+                                                      int64_t nrows, int64_t trow_off, int64_t pc0, int64_t lc0,
+                                                      int64_t ncols, int64_t col0, int64_t tile_rows,
+                                                      int64_t tile_cols, int seg_rows, int64_t q0, int64_t nunits,
+                                                      uint32_t *__restrict__ part, int64_t ti_base, int64_t ntr,
+                                                      int64_t tcols) {
+    typedef DigestUnit<G> U;
+    constexpr int NL = U::NL;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const int64_t ncb = (nunits + 63) / 64, nseg = (nrows + seg_rows - 1) / seg_rows;
+    const DigestShift h = digest_shift_of(pc0, lc0);
+    const int last = h.s ? NL : NL - 1;   // the unit's last canonical word that can hold a cell
+    for (int64_t item = wave; item < ncb * nseg; item += nwaves) {
+        const int64_t seg = item / ncb, cb = item % ncb;
+        const bool on = cb * 64 + lane < nunits;
+        const int64_t q = on ? q0 + cb * 64 + lane : q0;
+        uint32_t mask[NL], acc[NL + 1];
+        int64_t tc[NL + 1];
+#pragma unroll
+        for (int t = 0; t < NL; ++t) mask[t] = on ? digest_mask(NL * q + t, pc0, pc0 + ncols) : 0u;
+#pragma unroll
+        for (int t = 0; t <= NL; ++t) {
+            tc[t] = on ? density_tile_of(NL * q + h.dq + t, col0, tile_cols) : -1;   // (idle lanes: a tile of their own)
+            acc[t] = 0u;
+        }
+        const bool whole = __all(!on || density_is_whole<G>(mask, h.s, tc));   // (wave-uniform)
+        const bool one_tile = __all(tc[0] == tc[last]);
+        const int64_t ra = seg * seg_rows, rb = ra + seg_rows < nrows ? ra + seg_rows : nrows;
+        for (int64_t r = ra; r < rb;) {
+            // rows [r, re) of the segment lie in tile row ti
+            const int64_t ti = (trow_off + r) / tile_rows;
+            int64_t re = (ti + 1) * tile_rows - trow_off;
+            re = re < rb ? re : rb;
+            const int n = (int)(re - r);
+            const uint8_t *p = buf + (r0 + r) * pitch_bytes + q * U::BYTES;
+            // four rows' loads are issued before the first is used (digest_kernel); a row
+            // past the tile row's last is the last row again and is not counted
+            for (int j0 = 0; j0 < n; j0 += 4) {
+                uint4 x[4][U::WORDS / 4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int j = j0 + u < n ? j0 + u : n - 1;
+#pragma unroll
+                    for (int v = 0; v < U::WORDS / 4; ++v)
+                        x[u][v] = reinterpret_cast<const uint4 *>(p + j * pitch_bytes)[v];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (j0 + u >= n) break;   // (wave-uniform)
+                    uint32_t w[U::WORDS];
+#pragma unroll
+                    for (int v = 0; v < U::WORDS / 4; ++v) {
+                        w[4 * v] = x[u][v].x;
+                        w[4 * v + 1] = x[u][v].y;
+                        w[4 * v + 2] = x[u][v].z;
+                        w[4 * v + 3] = x[u][v].w;
+                    }
+                    if (whole) acc[0] += on ? density_unit_whole<G>(w) : 0u;
+                    else density_unit<G>(w, mask, h.s, acc);
+                }
+            }
+            // flush the tile row's counts (a count that is not 0 has a cell of the window
+            // in it, so its tile is inside the part; the range tests only repeat that)
+            const int64_t tr = ti - ti_base;
+            uint32_t *const prow = part + tr * tcols;
+            const bool tr_ok = tr >= 0 && tr < ntr;
+            if (one_tile) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int t = 0; t <= NL; ++t) v += acc[t];
+                const int key = (int)tc[0];
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t ov = __shfl_down(v, off, 64);
+                    const int ok = __shfl_down(key, off, 64);
+                    if (lane + off < 64 && ok == key) v += ov;
+                }
+                const int before = __shfl_up(key, 1, 64);
+                if ((lane == 0 || before != key) && v && tr_ok && key >= 0 && key < tcols) atomicAdd(prow + key, v);
+            } else {
+                uint32_t v = acc[0];
+                int64_t key = tc[0];
+#pragma unroll
+                for (int t = 1; t <= NL; ++t) {
+                    if (tc[t] == key) {
+                        v += acc[t];
+                    } else {
+                        if (v && tr_ok && key >= 0 && key < tcols) atomicAdd(prow + key, v);
+                        key = tc[t];
+                        v = acc[t];
+                    }
+                }
+                if (v && tr_ok && key >= 0 && key < tcols) atomicAdd(prow + key, v);
+            }
+#pragma unroll
+            for (int t = 0; t <= NL; ++t) acc[t] = 0u;
+            r = re;
+        }
+    }
+}
+
+hipError_t launch_density(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t trow_off, int64_t pc0,
+                          int64_t lc0, int64_t ncols, int64_t col0, int64_t tile_rows, int64_t tile_cols,
+                          uint32_t *part, int64_t ti_base, int64_t ntr, int64_t tcols, int bit_gw, hipStream_t s) {
+    const int64_t nrows = r1 - r0;
+    if (nrows <= 0 || ncols <= 0) return hipSuccess;
+    if (r0 < 0 || pc0 < 0 || col0 < 0 || lc0 < col0 || trow_off < 0 || tile_rows < 1 || tile_cols < 32 ||
+        tile_cols % 32 || col0 % 32 || (bit_gw != 0 && bit_gw != 2 && bit_gw != 4))
+        return hipErrorInvalidValue;
+    // every tile the run touches lies inside the part
+    if (trow_off / tile_rows < ti_base || (trow_off + nrows - 1) / tile_rows - ti_base >= ntr ||
+        (lc0 + ncols - 1 - col0) / tile_cols >= tcols || tcols > INT32_MAX)
+        return hipErrorInvalidValue;
+    const int64_t ucols = bit_gw ? DigestUnit<2>::COLS : DigestUnit<0>::COLS;
+    const int64_t q0 = pc0 / ucols, nunits = (pc0 + ncols - 1) / ucols - q0 + 1;
+    const int64_t ncb = (nunits + 63) / 64;
+    // segments of 64·m rows, chosen as launch_digest chooses them (tile rows cut them further)
+    constexpr int64_t kMaxBlocks = 4096;
+    int64_t m = (nrows + 63) / 64 * ncb / (kMaxBlocks * 4);
+    m = m < 1 ? 1 : m > 8 ? 8 : m;
+    int seg_rows = (int)(64 * m);
+    const int64_t items = ncb * ((nrows + seg_rows - 1) / seg_rows);
+    int64_t blocks = (items + 3) / 4;
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+    const auto fn = bit_gw == 4 ? density_kernel<4> : bit_gw == 2 ? density_kernel<2> : density_kernel<0>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const uint8_t *>(buf), pitch_bytes, r0,
+                       nrows, trow_off, pc0, lc0, ncols, col0, tile_rows, tile_cols, seg_rows, q0, nunits, part, ti_base,
+                       ntr, tcols);
     return hipGetLastError();
 }
 

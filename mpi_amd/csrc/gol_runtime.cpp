@@ -163,6 +163,21 @@ struct PendingDigest {
 };
 constexpr size_t kDigestRing = 1024;   // digests pending per context at most
 
+// A density map enqueued by gol_density_async: every slab that holds rows of the
+// window has a part of its own (the tile rows ti0 .. ti0 + ntr - 1 its rows
+// touch, tcols counts each) in pooled staging; sync_all clears the caller's
+// trows × tcols block and adds the parts (a tile that straddles a slab seam gets
+// both slabs' counts).
+struct PendingDensity {
+    struct Part {
+        size_t stage = 0;   // index into gol_ctx::staging
+        int64_t ti0 = 0, ntr = 0;
+    };
+    uint32_t *out = nullptr;   // caller's counts, leading dimension ld
+    int64_t ld = 0, trows = 0, tcols = 0;
+    std::vector<Part> parts;
+};
+
 // The schedule trial of the k=8 bit kernel (see tune_slot).
 // (2-word groups: six rounds are the default; 4-word groups: guided, 4 rounds;
 // the first candidate is the default, see common_create)
@@ -270,6 +285,7 @@ struct gol_ctx {
     std::vector<Staging> staging;
     std::vector<size_t> release_at_sync;   // staging of a failed async copy: busy until the next sync
     std::vector<PendingDigest> pending_digests;   // gol_digest_async (slot = index)
+    std::vector<PendingDensity> pending_density;  // gol_density_async
     // clock probe (gol_clock_start / gol_clock_stop)
     hipStream_t clk_stream = nullptr;
     unsigned long long *clk_out = nullptr;   // device: memtime0, realtime0, memtime1, realtime1
@@ -1171,6 +1187,26 @@ int sync_all(gol_ctx *c, double *elapsed_ms) {
             for (auto &s : c->slabs) v += s.dg_host[2 * j + i];
             dg[j].out[i] = v;
         }
+    // maps enqueued by gol_density_async: the whole block is written, the slabs' parts add
+    std::vector<PendingDensity> dn;
+    dn.swap(c->pending_density);
+    for (auto &m : dn) {
+        // one slab holding every tile row (the usual case): its part is the map and is copied;
+        // else the block is cleared and the parts are added
+        const bool whole = m.parts.size() == 1 && m.parts[0].ntr == m.trows;
+        for (int64_t i = 0; i < m.trows && !whole; ++i) memset(m.out + i * m.ld, 0, (size_t)m.tcols * sizeof(uint32_t));
+        for (auto &p : m.parts) {
+            Staging &b = c->staging[p.stage];
+            for (int64_t i = 0; i < p.ntr; ++i) {
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(b.pinned) + i * m.tcols;
+                uint32_t *dst = m.out + (p.ti0 + i) * m.ld;
+                if (whole) memcpy(dst, src, (size_t)m.tcols * sizeof(uint32_t));
+                else
+                    for (int64_t j = 0; j < m.tcols; ++j) dst[j] += src[j];
+            }
+            b.busy = false;
+        }
+    }
     if (elapsed_ms) *elapsed_ms = ms_max;
     return GOL_OK;
 }
@@ -1404,6 +1440,122 @@ int digest_now(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t nc
     }
     digest[0] = v[0];
     digest[1] = v[1];
+    return GOL_OK;
+}
+
+// ---------------------------------------------------------------------- density
+
+// ceil(nrows / tile_rows) × ceil(ncols / tile_cols)
+void density_dims(int64_t nrows, int64_t ncols, int64_t tile_rows, int64_t tile_cols, int64_t *trows, int64_t *tcols) {
+    *trows = nrows / tile_rows + (nrows % tile_rows != 0);
+    *tcols = ncols / tile_cols + (ncols % tile_cols != 0);
+}
+
+// Enqueue the density map (gol_density.h) of the window as it stands after every
+// step enqueued so far.  Per slab that holds rows of the window, on its compute
+// stream behind the joins digest_enqueue makes: the slab's part (pooled staging:
+// the tile rows its rows touch) is cleared, one launch per storage-contiguous
+// column run adds the cells of the window this slab holds (exact ranges, as the
+// digest's), and the part goes to its pinned mirror; sync_all adds the parts into
+// `counts`.  All staging is acquired before anything is enqueued and `counts` is
+// registered only once every slab is enqueued: a failed call leaves no pending
+// write (its staging stays busy until the next sync, as work may be in flight).
+int density_enqueue(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int64_t tile_rows,
+                    int64_t tile_cols, uint32_t *counts, int64_t ld) {
+    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
+        return fail(c, GOL_EINVAL, "window outside the grid");
+    if (tile_rows < 1) return fail(c, GOL_EINVAL, "tile_rows < 1");
+    if (tile_cols < 32 || tile_cols % 32) return fail(c, GOL_EINVAL, "tile_cols must be a multiple of 32 (>= 32)");
+    if (col0 % 32) return fail(c, GOL_EINVAL, "col0 must be a multiple of 32");
+    if (tile_rows > (int64_t)0xffffffffll / tile_cols)
+        return fail(c, GOL_EINVAL, "a tile of more than 2^32 - 1 cells (a count is 32 bits)");
+    int64_t trows = 0, tcols = 0;
+    density_dims(nrows, ncols, tile_rows, tile_cols, &trows, &tcols);
+    if (ld < tcols) return fail(c, GOL_EINVAL, "ld < tcols");
+    if (nrows == 0 || ncols == 0) return GOL_OK;
+    struct Piece {
+        Slab *s;
+        int64_t r0, r1;
+        PendingDensity::Part part;
+    };
+    std::vector<Piece> pieces;
+    for (auto &s : c->slabs) {
+        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
+        if (r1 <= r0) continue;   // nothing of the window here: this slab adds nothing
+        Piece p{&s, r0, r1, {}};
+        p.part.ti0 = (r0 - row0) / tile_rows;
+        p.part.ntr = (r1 - 1 - row0) / tile_rows - p.part.ti0 + 1;
+        if (int rc = acquire_staging(c, s.device, (size_t)(p.part.ntr * tcols) * sizeof(uint32_t), &p.part.stage)) {
+            for (auto &q : pieces) c->staging[q.part.stage].busy = false;   // nothing enqueued yet
+            return rc;
+        }
+        pieces.push_back(p);
+    }
+    const int gw = c->layout == GOL_LAYOUT_BIT ? c->gw : 0;
+    auto enqueue = [&](const Piece &p) -> int {
+        Slab &s = *p.s;
+        Staging &buf = c->staging[p.part.stage];
+        uint32_t *d = reinterpret_cast<uint32_t *>(buf.dtmp);
+        const size_t bytes = (size_t)(p.part.ntr * tcols) * sizeof(uint32_t);
+        HIPCHK(c, hipSetDevice(s.device));
+        // the last step's boundary bands run on the comm stream: join it
+        hipEvent_t e;
+        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        const hipError_t e1 = tr_record(c, e, s.comm);
+        const hipError_t e2 = e1 == hipSuccess ? tr_wait(c, s.comp, e) : e1;
+        (void)hipEventDestroy(e);
+        HIPCHK(c, e2);
+        if (int rc = join_parts(c, s, s.comp)) return rc;   // (a split interior's other parts)
+        const int64_t srow = c->hk + (p.r0 - s.row0);
+        tr_op(c, TR_READ, s.comp, nullptr, s.index, c->cur, srow, srow + (p.r1 - p.r0));
+        HIPCHK(c, hipMemsetAsync(d, 0, bytes, s.comp));
+        int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
+            HIPCHK(c, launch_density(s.buf[c->cur], c->pitch_bytes, srow, srow + (p.r1 - p.r0), p.r0 - row0, pc, lc, n,
+                                     col0, tile_rows, tile_cols, d, p.part.ti0, p.part.ntr, tcols, gw, s.comp));
+            return GOL_OK;
+        });
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(buf.pinned, d, bytes, hipMemcpyDeviceToHost, s.comp));
+        // as window_async: the slab's other streams wait for the read before a later
+        // step (the step after next) overwrites this buffer
+        if (s.nx || s.comm != s.comp) {
+            hipEvent_t f;
+            HIPCHK(c, hipEventCreateWithFlags(&f, hipEventDisableTiming));
+            hipError_t f1 = tr_record(c, f, s.comp);
+            if (f1 == hipSuccess && s.comm != s.comp) f1 = tr_wait(c, s.comm, f);
+            for (int j = 0; j < s.nx && f1 == hipSuccess; ++j) f1 = tr_wait(c, s.part[j], f);
+            (void)hipEventDestroy(f);
+            HIPCHK(c, f1);
+        }
+        return GOL_OK;
+    };
+    for (const auto &p : pieces) {
+        if (int rc = enqueue(p)) {
+            for (auto &q : pieces) c->release_at_sync.push_back(q.part.stage);
+            return rc;
+        }
+    }
+    PendingDensity m;
+    m.out = counts;
+    m.ld = ld;
+    m.trows = trows;
+    m.tcols = tcols;
+    for (const auto &p : pieces) m.parts.push_back(p.part);
+    c->pending_density.push_back(m);
+    return GOL_OK;
+}
+
+// The synchronising forms.
+int density_now(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int64_t tile_rows,
+                int64_t tile_cols, uint32_t *counts, int64_t ld) {
+    if (int rc = density_enqueue(c, row0, col0, nrows, ncols, tile_rows, tile_cols, counts, ld)) return rc;
+    if (int rc = sync_all(c, nullptr)) {
+        // not delivered: the caller's block is not written later either
+        for (auto &m : c->pending_density)
+            for (auto &p : m.parts) c->release_at_sync.push_back(p.stage);
+        c->pending_density.clear();
+        return rc;
+    }
     return GOL_OK;
 }
 
@@ -2371,6 +2523,29 @@ int gol_digest_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int
 int gol_digest_async(gol_ctx *c, uint64_t digest[2]) {
     if (!c || !digest) return GOL_EINVAL;
     return digest_enqueue(c, 0, 0, c->rows, c->cols, digest);
+}
+
+int gol_density_dims(int64_t nrows, int64_t ncols, int64_t tile_rows, int64_t tile_cols, int64_t *trows,
+                     int64_t *tcols) {
+    if (!trows || !tcols || nrows < 0 || ncols < 0 || tile_rows < 1 || tile_cols < 1) return GOL_EINVAL;
+    density_dims(nrows, ncols, tile_rows, tile_cols, trows, tcols);
+    return GOL_OK;
+}
+
+int gol_density(gol_ctx *c, int64_t tile_rows, int64_t tile_cols, uint32_t *counts, int64_t ld) {
+    if (!c || !counts) return GOL_EINVAL;
+    return density_now(c, 0, 0, c->rows, c->cols, tile_rows, tile_cols, counts, ld);
+}
+
+int gol_density_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int64_t tile_rows,
+                       int64_t tile_cols, uint32_t *counts, int64_t ld) {
+    if (!c || !counts) return GOL_EINVAL;
+    return density_now(c, row0, col0, nrows, ncols, tile_rows, tile_cols, counts, ld);
+}
+
+int gol_density_async(gol_ctx *c, int64_t tile_rows, int64_t tile_cols, uint32_t *counts, int64_t ld) {
+    if (!c || !counts) return GOL_EINVAL;
+    return density_enqueue(c, 0, 0, c->rows, c->cols, tile_rows, tile_cols, counts, ld);
 }
 
 // The probe's stream: ONE per device for the whole process (never destroyed).

@@ -48,6 +48,7 @@ EXPORTS = [
     "gol_read_text", "gol_download_window_async", "gol_clock_start", "gol_clock_stop", "gol_rccl_selftest",
     "gol_sched_trace", "gol_comm_time", "gol_parse_rule", "gol_set_rule", "gol_get_rule",
     "gol_digest", "gol_digest_window", "gol_digest_async",
+    "gol_density_dims", "gol_density", "gol_density_window", "gol_density_async",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -113,6 +114,10 @@ def load() -> ctypes.CDLL:
         "gol_digest": ([P, ctypes.POINTER(ctypes.c_uint64)], i32),
         "gol_digest_window": ([P, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_uint64)], i32),
         "gol_digest_async": ([P, ctypes.POINTER(ctypes.c_uint64)], i32),
+        "gol_density_dims": ([i64, i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
+        "gol_density": ([P, i64, i64, ctypes.POINTER(u32), i64], i32),
+        "gol_density_window": ([P, i64, i64, i64, i64, i64, i64, ctypes.POINTER(u32), i64], i32),
+        "gol_density_async": ([P, i64, i64, ctypes.POINTER(u32), i64], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -143,6 +148,16 @@ def parse_rule(text: str) -> tuple[int, int]:
     if rc:
         raise GolError(rc, f"gol_parse_rule: not a B/S rule: {text!r}")
     return b.value, s.value
+
+
+def density_dims(nrows: int, ncols: int, tile_rows: int, tile_cols: int) -> tuple[int, int]:
+    """(trows, tcols) of the density map of a nrows × ncols window: ceil(nrows / tile_rows),
+    ceil(ncols / tile_cols).  Host-only."""
+    tr, tc = ctypes.c_int64(), ctypes.c_int64()
+    rc = load().gol_density_dims(nrows, ncols, tile_rows, tile_cols, ctypes.byref(tr), ctypes.byref(tc))
+    if rc:
+        raise GolError(rc, "gol_density_dims: sizes >= 0 and tiles >= 1")
+    return tr.value, tc.value
 
 
 def unique_id() -> bytes:
@@ -185,6 +200,10 @@ def part_geometry(path: str) -> tuple[int, int, int, int, int]:
 
 def _u8(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
+def _u32(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
 
 
 class Engine:
@@ -365,6 +384,37 @@ class Engine:
                     return seen[key], g
                 seen[key] = g
         return None
+
+    # ------------------------------------------------------------ density
+    def density(self, tile_rows: int, tile_cols: int | None = None) -> np.ndarray:
+        """Live cells per tile of tile_rows × tile_cols cells (tile_cols: a multiple of 32,
+        default tile_rows), computed on the device: a uint32 array of shape
+        density_dims(rows, cols, ...), equal to the map of download()
+        (tests/density_ref.py); edge tiles are clipped to the board.  Rank contexts return
+        the counts of their own rows (0 elsewhere); the maps add.  Synchronises."""
+        return self.density_window(0, 0, self.rows, self.cols, tile_rows, tile_cols)
+
+    def density_window(self, row0: int, col0: int, nrows: int, ncols: int, tile_rows: int,
+                       tile_cols: int | None = None) -> np.ndarray:
+        """Density map of a window (global coordinates, col0 a multiple of 32), tiles
+        counted from its origin.  Synchronises."""
+        tile_cols = tile_rows if tile_cols is None else tile_cols
+        out = np.zeros(density_dims(nrows, ncols, tile_rows, tile_cols), np.uint32)
+        ld = max(1, out.shape[1])
+        self._chk(self.lib.gol_density_window(self._c, row0, col0, nrows, ncols, tile_rows, tile_cols, _u32(out), ld),
+                  "gol_density_window")
+        self._pending = []
+        return out
+
+    def density_async(self, tile_rows: int, tile_cols: int | None = None) -> np.ndarray:
+        """Enqueue a whole-board density map behind the steps enqueued so far; the
+        returned uint32 array is filled by the next synchronising call."""
+        tile_cols = tile_rows if tile_cols is None else tile_cols
+        out = np.zeros(density_dims(self.rows, self.cols, tile_rows, tile_cols), np.uint32)
+        self._chk(self.lib.gol_density_async(self._c, tile_rows, tile_cols, _u32(out), max(1, out.shape[1])),
+                  "gol_density_async")
+        self._pending.append(out)   # kept alive here until a synchronising call has filled it
+        return out
 
     def clock_start(self, max_ms: float):
         """Start the clock probe (one wave on its own stream, stops by itself after max_ms)."""
