@@ -235,7 +235,37 @@ int gol_download_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows,
 int gol_download_window_async(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
                               uint8_t *host, int64_t ld);
 
-/* Snapshot text — the body of a `.gol` part file as writeBoardToFile writes it
+/* 1-bit-per-cell board I/O: the calls above with packed rows, an eighth of the
+ * bytes on every transfer.  Row i of the window starts at host + i*ld (ld in
+ * BYTES, ld >= gol_bits_row_bytes(ncols) = (ncols + 7) / 8); column col0 + j is bit
+ * 7 - (j & 7) of byte j >> 3 of its row, MSB first, 1 = live: numpy's
+ * packbits(window, axis=1) and the raster of a PBM `P4` image.  The format is
+ * defined on bytes (no endianness); col0 and ncols are arbitrary.  The packing runs
+ * on the device; the result equals packbits of what gol_download[_window] returns,
+ * for every layout, group width, tblock_k, boundary storage (torus ghost columns,
+ * MESH_COMPAT's reversed blocks), slab count and transport.
+ *   download: the 8*row_bytes - ncols pad bits of a row's last byte are written as
+ *             0; bytes [row_bytes, ld) of a row are not touched.
+ *   upload:   pad bits are ignored; only the window's cells change; cells outside
+ *             the active region (SERIAL_COMPAT: last row and column) are stored as 0.
+ * Rank contexts move the rows they hold, as the byte calls do; the _async form
+ * needs every row held, is enqueued behind every gol_step so far and is delivered
+ * by the next synchronising call (a failed call leaves no pending write).  Staging
+ * comes from the context's pool (see gol_clock_start).  GOL_EINVAL with a message:
+ * window outside the grid, ld too small, a null buffer.  An empty window is GOL_OK
+ * and writes nothing.  gol_bits_row_bytes: host only; ncols < 0 gives GOL_EINVAL.
+ * No reference counterpart. */
+int64_t gol_bits_row_bytes(int64_t ncols);
+int gol_download_bits(gol_ctx *ctx, uint8_t *host, int64_t ld);
+int gol_download_bits_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
+                             uint8_t *host, int64_t ld);
+int gol_download_bits_window_async(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
+                                   uint8_t *host, int64_t ld);
+int gol_upload_bits(gol_ctx *ctx, const uint8_t *host, int64_t ld);
+int gol_upload_bits_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
+                           const uint8_t *host, int64_t ld);
+
+/* Snapshot text —the body of a `.gol` part file as writeBoardToFile writes it
  * (main.cpp:106-129, main_serial.cpp:74-95; read back by
  * gol_visualization.py:29-33): for every row of the window one "0\t" or "1\t"
  * per cell, then "\n".  The two header lines ("firstRow lastRow" /

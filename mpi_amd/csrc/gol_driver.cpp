@@ -35,6 +35,15 @@
 //                           iteration I (part files NAME_I_<p>.gol, read back
 //                           on the device); rows/cols/gap/iters default to the
 //                           main file's; new snapshots continue under NAME
+//   --format gol|pbm        the snapshot parts' format (default gol: the reference's text).
+//                           pbm: part files `<name>_<iter>_<part>.pbm`, binary PBM —
+//                           "P4\n# gol <firstRow> <lastRow> <firstCol> <lastCol>\n<ncols> <nrows>\n"
+//                           (the comment carries the four numbers of the .gol header
+//                           lines), then the raster: rows of ceil(ncols / 8) bytes, MSB
+//                           first, 1 = live, packed on the device
+//                           (gol_download_bits_window) — a sixteenth of the text's
+//                           bytes, and any image tool opens it.  With --resume the
+//                           parts NAME_I_<p>.pbm are read back (gol_upload_bits_window)
 //   --rccl                  the N row slabs as N RCCL ranks of ONE process: one
 //                           rank context (gol_create_rank) and one communicator
 //                           per device, each driven by a host thread, halo rows
@@ -152,8 +161,56 @@ void read_part(gol_ctx *ctx, const std::string &path) {
     close(fd);
 }
 
+// --format pbm: the part as a binary PBM, the raster downloaded packed in row blocks of
+// at most 64 MiB.  The comment line carries write_part's four header numbers.
+constexpr int64_t kPbmBlock = 64LL << 20;
+void write_part_pbm(gol_ctx *ctx, const std::string &name, int iter, int part, long first_row, long last_row,
+                    long first_col, long last_col, int64_t row0, int64_t nrows, int64_t ncols) {
+    std::string path = name + "_" + std::to_string(iter) + "_" + std::to_string(part) + ".pbm";
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) die("cannot create part .pbm file");
+    fprintf(f, "P4\n# gol %ld %ld %ld %ld\n%lld %lld\n", first_row, last_row, first_col, last_col, (long long)ncols,
+            (long long)nrows);
+    const int64_t rb = gol_bits_row_bytes(ncols), br = std::max<int64_t>(1, kPbmBlock / std::max<int64_t>(1, rb));
+    std::vector<uint8_t> buf((size_t)(std::min(br, nrows) * rb));
+    for (int64_t a = 0; a < nrows; a += br) {
+        const int64_t n = std::min(br, nrows - a);
+        check(ctx, gol_download_bits_window(ctx, row0 + a, 0, n, ncols, buf.data(), rb), "gol_download_bits_window");
+        if (fwrite(buf.data(), 1, (size_t)(n * rb), f) != (size_t)(n * rb)) die(("cannot write " + path).c_str());
+    }
+    if (fclose(f) != 0) die(("cannot write " + path).c_str());
+}
+
+// Snapshot resume from a .pbm part: the origin is the first and third number of the
+// comment, the shape the size line's; the raster must be complete.
+void read_part_pbm(gol_ctx *ctx, const std::string &path) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) die(("cannot open " + path).c_str());
+    long r0 = 0, r_end = 0, c0 = 0, c_end = 0;
+    long long ncols = 0, nrows = 0;
+    char magic[3] = {0, 0, 0};
+    if (fread(magic, 1, 3, f) != 3 || memcmp(magic, "P4\n", 3) != 0 ||
+        fscanf(f, "# gol %ld %ld %ld %ld", &r0, &r_end, &c0, &c_end) != 4 || fgetc(f) != '\n' ||
+        fscanf(f, "%lld %lld", &ncols, &nrows) != 2 || fgetc(f) != '\n' || r0 < 0 || c0 < 0 || ncols < 1 || nrows < 1)
+        die(("bad header in " + path).c_str());
+    const long off = ftell(f);
+    fseek(f, 0, SEEK_END);
+    const long size = ftell(f);
+    const int64_t rb = gol_bits_row_bytes(ncols);
+    if (size - off != nrows * rb) die(("bad body in " + path + ": the raster is short or long").c_str());
+    fseek(f, off, SEEK_SET);
+    const int64_t br = std::max<int64_t>(1, kPbmBlock / rb);
+    std::vector<uint8_t> buf((size_t)(std::min<int64_t>(br, nrows) * rb));
+    for (int64_t a = 0; a < nrows; a += br) {
+        const int64_t n = std::min<int64_t>(br, nrows - a);
+        if (fread(buf.data(), 1, (size_t)(n * rb), f) != (size_t)(n * rb)) die(("cannot read " + path).c_str());
+        check(ctx, gol_upload_bits_window(ctx, r0 + a, c0, n, ncols, buf.data(), rb), path.c_str());
+    }
+    fclose(f);
+}
+
 struct Opts {
-    std::string mode = "mpi", layout = "";
+    std::string mode = "mpi", layout = "", format = "gol";
     int procs = 1, gpus = 1, k = 1, save = -1;
     long long seed = -1;
     std::string resume;   // --resume NAME: continue the run whose main file is NAME.gol
@@ -223,6 +280,7 @@ int main(int argc, char **argv) {
         else if (a == "--layout") o.layout = next();
         else if (a == "-k") o.k = atoi(next());
         else if (a == "--rule") o.rule = next();
+        else if (a == "--format") o.format = next();
         else if (a == "--save") o.save = 1;
         else if (a == "--no-save") o.save = 0;
         else if (a == "--seed") o.seed = atoll(next());
@@ -249,6 +307,8 @@ int main(int argc, char **argv) {
         }
         else pos.push_back(argv[i]);
     }
+    if (o.format != "gol" && o.format != "pbm") die("--format must be gol or pbm");
+    const bool pbm = o.format == "pbm";
     long m_rows = 0, m_cols = 0;
     int m_gap = 0, m_iters = 0, m_parts = 0;
     if (!o.resume.empty()) {
@@ -346,10 +406,11 @@ int main(int argc, char **argv) {
     if (o.rccl) check(nullptr, gol_get_unique_id(uid), "gol_get_unique_id");
     // part p of a snapshot: the rows of slab p, written by the context holding them
     auto write_snap = [&](gol_ctx *ctx, int iter, int p) {
+        const auto part = pbm ? write_part_pbm : write_part;
         if (o.mode == "serial" && parts == 1)   // main_serial.cpp:164-167: "0 n" / "0 n"
-            write_part(ctx, name, iter, p, 0, rows, 0, cols, 0, rows, cols);
+            part(ctx, name, iter, p, 0, rows, 0, cols, 0, rows, cols);
         else   // main.cpp:255-258: inclusive ranges (gol_visualization.py:33 slices [min, max+1])
-            write_part(ctx, name, iter, p, row0[p], row0[p] + nrow[p] - 1, 0, cols - 1, row0[p], nrow[p], cols);
+            part(ctx, name, iter, p, row0[p], row0[p] + nrow[p] - 1, 0, cols - 1, row0[p], nrow[p], cols);
     };
     // set-up of context i (rank i under --rccl): create, then the board
     auto set_up = [&](int i) {
@@ -368,7 +429,8 @@ int main(int argc, char **argv) {
         } else {
             for (int p = 0; p < m_parts; ++p)
                 if (!o.rccl || p == i)
-                    read_part(ctx, o.resume + "_" + std::to_string(from) + "_" + std::to_string(p) + ".gol");
+                    (pbm ? read_part_pbm : read_part)(ctx, o.resume + "_" + std::to_string(from) + "_" +
+                                                               std::to_string(p) + (pbm ? ".pbm" : ".gol"));
         }
         // main_serial.cpp:171 writes generation 0; main.cpp:285 has that write commented out, which
         // leaves gol_visualization.py without its iteration-0 files, so every saving mode writes it.

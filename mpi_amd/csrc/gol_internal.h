@@ -188,4 +188,20 @@ hipError_t launch_density(const void *buf, int64_t pitch_bytes, int64_t r0, int6
                           int64_t lc0, int64_t ncols, int64_t col0, int64_t tile_rows, int64_t tile_cols,
                           uint32_t *part, int64_t ti_base, int64_t ntr, int64_t tcols, int bit_gw, hipStream_t s);
 
+// ---- gol_download_bits* / gol_upload_bits*: 1-bit-per-cell rows (gol_bits.h, gol_bits.hip) ----
+// launch_digest's cells: storage rows [r0, r1) × storage columns [pc0, pc0 + ncols),
+// storage column pc0 being column lc0 of the WINDOW (>= 0).  The packed buffer holds
+// one row of pitch_words u32 per storage row, row r0 first: bytes MSB first, window
+// column j at bit 7 - (j & 7) of byte j >> 3.  A run whose last word
+// (lc0 + ncols - 1) / 32 is not below pitch_words is hipErrorInvalidValue.
+// get: the cells are OR-ed into `out` (the caller clears it; launches that share words
+// are ordered on one stream), only words that hold cells of the run are written.
+// put: exactly these cells change; storage columns >= active_cols are stored as 0;
+// every other bit of `in` is ignored.
+hipError_t launch_get_bits(const void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t pc0, int64_t lc0,
+                           int64_t ncols, uint32_t *out, int64_t out_pitch_words, int bit_gw, hipStream_t s);
+hipError_t launch_put_bits(void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t pc0, int64_t lc0,
+                           int64_t ncols, int64_t active_cols, const uint32_t *in, int64_t in_pitch_words, int bit_gw,
+                           hipStream_t s);
+
 } // namespace gol

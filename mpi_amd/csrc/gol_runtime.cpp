@@ -153,7 +153,8 @@ struct Staging {
 struct PendingWindow {
     size_t stage = 0;          // index into gol_ctx::staging
     uint8_t *host = nullptr;   // caller's rows, leading dimension ld
-    int64_t ld = 0, nrows = 0, ncols = 0;
+    int64_t ld = 0, nrows = 0, ncols = 0;   // ncols: bytes delivered per row
+    int64_t pitch = 0;         // bytes between staging rows (0: ncols; packed rows: whole dwords)
 };
 
 // A digest enqueued by gol_digest_async: pending digest j owns slot j of every
@@ -1175,7 +1176,8 @@ int sync_all(gol_ctx *c, double *elapsed_ms) {
     pend.swap(c->pending);
     for (auto &w : pend) {
         Staging &b = c->staging[w.stage];
-        for (int64_t r = 0; r < w.nrows; ++r) memcpy(w.host + r * w.ld, b.pinned + r * w.ncols, (size_t)w.ncols);
+        const int64_t sp = w.pitch ? w.pitch : w.ncols;
+        for (int64_t r = 0; r < w.nrows; ++r) memcpy(w.host + r * w.ld, b.pinned + r * sp, (size_t)w.ncols);
         b.busy = false;
     }
     // digests enqueued by gol_digest_async: the slabs' parts add (mod 2^64)
@@ -1261,6 +1263,11 @@ int acquire_staging(gol_ctx *c, int device, size_t bytes, size_t *idx) {
     return GOL_OK;
 }
 
+// 1-bit-per-cell rows (gol_bits.h): bytes a caller's row holds, and the pitch of a
+// staging row (whole dwords: the kernels store and load u32 words).
+int64_t bits_row_bytes(int64_t ncols) { return (ncols + 7) / 8; }
+int64_t bits_pitch(int64_t ncols) { return (ncols + 31) / 32 * 4; }
+
 // Enqueue a copy of a window as it stands after every step enqueued so far:
 // unpack (bit) or gather (byte) into device staging on the slab's compute
 // stream, then an async D2H copy into pinned staging; sync_all delivers it.
@@ -1268,11 +1275,18 @@ int acquire_staging(gol_ctx *c, int device, size_t bytes, size_t *idx) {
 // buffer is registered for delivery only once every slab's copy is enqueued:
 // a failed call leaves no pending write into the caller's memory (its staging
 // stays busy until the next sync, as copies may be in flight).
-int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host, int64_t ld) {
+// packed (gol_download_bits*): the rows leave as bits, MSB first (gol_bits.h).  The
+// device staging holds packed rows of whole dwords (bits_pitch), cleared on the
+// compute stream before one launch_get_bits per column run ORs its cells in;
+// sync_all delivers gol_bits_row_bytes(ncols) bytes of each row.
+int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host, int64_t ld,
+                 bool packed = false) {
     if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
         return fail(c, GOL_EINVAL, "window outside the grid");
-    if (ld < ncols) return fail(c, GOL_EINVAL, "ld < ncols");
+    if (packed && ld < bits_row_bytes(ncols)) return fail(c, GOL_EINVAL, "ld < gol_bits_row_bytes(ncols)");
+    if (!packed && ld < ncols) return fail(c, GOL_EINVAL, "ld < ncols");
     if (nrows == 0 || ncols == 0) return GOL_OK;
+    const int64_t spitch = packed ? bits_pitch(ncols) : ncols;   // bytes per staging row
     int64_t held = 0;
     for (auto &s : c->slabs) held += std::max<int64_t>(0, std::min(row0 + nrows, s.row0 + s.H) - std::max(row0, s.row0));
     if (held != nrows) return fail(c, GOL_EINVAL, "window rows are not all held by this context");
@@ -1286,7 +1300,7 @@ int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t 
         const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
         if (r1 <= r0) continue;
         size_t st = 0;
-        if (int rc = acquire_staging(c, s.device, (size_t)((r1 - r0) * ncols), &st)) {
+        if (int rc = acquire_staging(c, s.device, (size_t)((r1 - r0) * spitch), &st)) {
             for (auto &p : pieces) c->staging[p.stage].busy = false;   // nothing enqueued yet
             return rc;
         }
@@ -1307,9 +1321,14 @@ int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t 
         if (int rc = join_parts(c, s, s.comp)) return rc;   // (a split interior's other parts)
         const int64_t srow = c->hk + (p.r0 - s.row0);
         tr_op(c, TR_READ, s.comp, nullptr, s.index, c->cur, srow, srow + nr);
+        if (packed) HIPCHK(c, hipMemsetAsync(buf.dtmp, 0, (size_t)(nr * spitch), s.comp));
         int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
             uint8_t *d = buf.dtmp + (lc - col0);
-            if (c->layout == GOL_LAYOUT_BYTE)
+            if (packed)
+                HIPCHK(c, launch_get_bits(s.buf[c->cur], c->pitch_bytes, srow, srow + nr, pc, lc - col0, n,
+                                          reinterpret_cast<uint32_t *>(buf.dtmp), spitch / 4,
+                                          c->layout == GOL_LAYOUT_BIT ? c->gw : 0, s.comp));
+            else if (c->layout == GOL_LAYOUT_BYTE)
                 HIPCHK(c, hipMemcpy2DAsync(d, ncols, static_cast<uint8_t *>(s.buf[c->cur]) + srow * c->pitch_bytes + pc,
                                            c->pitch_bytes, n, nr, hipMemcpyDeviceToDevice, s.comp));
             else
@@ -1318,7 +1337,7 @@ int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t 
             return GOL_OK;
         });
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(buf.pinned, buf.dtmp, (size_t)(nr * ncols), hipMemcpyDeviceToHost, s.comp));
+        HIPCHK(c, hipMemcpyAsync(buf.pinned, buf.dtmp, (size_t)(nr * spitch), hipMemcpyDeviceToHost, s.comp));
         // The other streams of the slab wait for later steps' events only, recorded after
         // other work than this copy on the compute stream (a split interior's parts wait for
         // seam bands; without overlap the whole step runs on the comm stream): they must
@@ -1347,7 +1366,8 @@ int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t 
         w.host = host + (p.r0 - row0) * ld;
         w.ld = ld;
         w.nrows = p.r1 - p.r0;
-        w.ncols = ncols;
+        w.ncols = packed ? bits_row_bytes(ncols) : ncols;
+        w.pitch = spitch;
         c->pending.push_back(w);
     }
     return GOL_OK;
@@ -1710,23 +1730,34 @@ int enforce_inactive(gol_ctx *c, Slab &s, int buf) {
 constexpr int64_t kIoBlock = 64LL << 20;
 
 // host rows [r0, r1) of the window -> slab s: pinned staging, H2D, then a
-// strided device copy + normalisation (byte) or the pack kernel (bit)
+// strided device copy + normalisation (byte) or the pack kernel (bit).
+// packed (gol_upload_bits*): the host rows are bits (gol_bits.h); they travel as
+// rows of whole dwords and one launch_put_bits per column run merges the run's
+// cells into the board (pad bits and the other runs' bits are masked out there).
 int upload_piece(gol_ctx *c, Slab &s, int64_t r0, int64_t r1, int64_t col0, int64_t ncols, const uint8_t *hrows,
-                 int64_t ld) {
+                 int64_t ld, bool packed = false) {
     const int64_t nr = r1 - r0;
+    const int64_t rowlen = packed ? bits_row_bytes(ncols) : ncols, spitch = packed ? bits_pitch(ncols) : ncols;
     size_t st = 0;
-    if (int rc = acquire_staging(c, s.device, (size_t)(nr * ncols), &st)) return rc;
+    if (int rc = acquire_staging(c, s.device, (size_t)(nr * spitch), &st)) return rc;
     Staging &b = c->staging[st];
-    for (int64_t r = 0; r < nr; ++r) memcpy(b.pinned + r * ncols, hrows + r * ld, (size_t)ncols);
+    for (int64_t r = 0; r < nr; ++r) {
+        memcpy(b.pinned + r * spitch, hrows + r * ld, (size_t)rowlen);
+        memset(b.pinned + r * spitch + rowlen, 0, (size_t)(spitch - rowlen));
+    }
     const int64_t srow = c->hk + (r0 - s.row0);
     uint8_t *board = static_cast<uint8_t *>(s.buf[c->cur]);
     auto enqueue = [&]() -> int {
         HIPCHK(c, hipSetDevice(s.device));
         tr_op(c, TR_WRITE, s.comp, nullptr, s.index, c->cur, srow, srow + nr);
-        HIPCHK(c, hipMemcpyAsync(b.dtmp, b.pinned, (size_t)(nr * ncols), hipMemcpyHostToDevice, s.comp));
+        HIPCHK(c, hipMemcpyAsync(b.dtmp, b.pinned, (size_t)(nr * spitch), hipMemcpyHostToDevice, s.comp));
         int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
             const uint8_t *cells = b.dtmp + (lc - col0);
-            if (c->layout == GOL_LAYOUT_BYTE) {
+            if (packed) {
+                HIPCHK(c, launch_put_bits(board, c->pitch_bytes, srow, srow + nr, pc, lc - col0, n, c->active_cols,
+                                          reinterpret_cast<const uint32_t *>(b.dtmp), spitch / 4,
+                                          c->layout == GOL_LAYOUT_BIT ? c->gw : 0, s.comp));
+            } else if (c->layout == GOL_LAYOUT_BYTE) {
                 uint8_t *d = board + srow * c->pitch_bytes + pc;
                 HIPCHK(c, hipMemcpy2DAsync(d, c->pitch_bytes, cells, ncols, n, nr, hipMemcpyDeviceToDevice, s.comp));
                 // cells are bools (main.cpp:73): any nonzero byte is a live cell
@@ -1750,13 +1781,15 @@ int upload_piece(gol_ctx *c, Slab &s, int64_t r0, int64_t r1, int64_t col0, int6
 }
 
 int window_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host, int64_t ld,
-              bool upload) {
+              bool upload, bool packed = false) {
     if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
         return fail(c, GOL_EINVAL, "window outside the grid");
-    if (ld < ncols) return fail(c, GOL_EINVAL, "ld < ncols");
+    if (packed && ld < bits_row_bytes(ncols)) return fail(c, GOL_EINVAL, "ld < gol_bits_row_bytes(ncols)");
+    if (!packed && ld < ncols) return fail(c, GOL_EINVAL, "ld < ncols");
     if (nrows == 0 || ncols == 0) return GOL_OK;
+    if (packed && !host) return fail(c, GOL_EINVAL, "null buffer");
     if (int rc = sync_all(c, nullptr)) return rc;
-    const int64_t br = std::max<int64_t>(1, kIoBlock / ncols);
+    const int64_t br = std::max<int64_t>(1, kIoBlock / (packed ? bits_pitch(ncols) : ncols));
     bool any = false;
     // slab by slab (a rank context moves the rows it holds; the others stay untouched)
     for (size_t si = 0; si < c->slabs.size(); ++si) {
@@ -1767,7 +1800,8 @@ int window_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t nco
         for (int64_t a = r0; a < r1; a += br) {
             const int64_t e = std::min(r1, a + br);
             uint8_t *h = host + (a - row0) * ld;
-            int rc = upload ? upload_piece(c, s, a, e, col0, ncols, h, ld) : window_async(c, a, col0, e - a, ncols, h, ld);
+            int rc = upload ? upload_piece(c, s, a, e, col0, ncols, h, ld, packed)
+                            : window_async(c, a, col0, e - a, ncols, h, ld, packed);
             if (!rc && !upload) rc = sync_all(c, nullptr);
             if (rc) return rc;
         }
@@ -2354,6 +2388,49 @@ int gol_download_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, i
                         int64_t ld) {
     if (!c || !host) return GOL_EINVAL;
     return window_io(c, row0, col0, nrows, ncols, host, ld, false);
+}
+
+int64_t gol_bits_row_bytes(int64_t ncols) {
+    if (ncols < 0) return GOL_EINVAL;
+    return bits_row_bytes(ncols);
+}
+
+// (a null buffer is refused with a message unless the window is empty: window_io, bits_window_async)
+int gol_download_bits(gol_ctx *c, uint8_t *host, int64_t ld) {
+    if (!c) return GOL_EINVAL;
+    if (c->transport == GOL_XPORT_RCCL && host) {
+        const Slab &s = c->slabs[0];
+        return window_io(c, s.row0, 0, s.H, c->cols, host + s.row0 * ld, ld, false, true);
+    }
+    return window_io(c, 0, 0, c->rows, c->cols, host, ld, false, true);
+}
+
+int gol_download_bits_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host,
+                             int64_t ld) {
+    if (!c) return GOL_EINVAL;
+    return window_io(c, row0, col0, nrows, ncols, host, ld, false, true);
+}
+
+int gol_download_bits_window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host,
+                                   int64_t ld) {
+    if (!c) return GOL_EINVAL;
+    if (!host && nrows > 0 && ncols > 0) return fail(c, GOL_EINVAL, "null buffer");
+    return window_async(c, row0, col0, nrows, ncols, host, ld, true);
+}
+
+int gol_upload_bits(gol_ctx *c, const uint8_t *host, int64_t ld) {
+    if (!c) return GOL_EINVAL;
+    if (c->transport == GOL_XPORT_RCCL && host) {
+        const Slab &s = c->slabs[0];
+        return window_io(c, s.row0, 0, s.H, c->cols, const_cast<uint8_t *>(host) + s.row0 * ld, ld, true, true);
+    }
+    return window_io(c, 0, 0, c->rows, c->cols, const_cast<uint8_t *>(host), ld, true, true);
+}
+
+int gol_upload_bits_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, const uint8_t *host,
+                           int64_t ld) {
+    if (!c) return GOL_EINVAL;
+    return window_io(c, row0, col0, nrows, ncols, const_cast<uint8_t *>(host), ld, true, true);
 }
 
 int64_t gol_text_bytes(int64_t nrows, int64_t ncols) {

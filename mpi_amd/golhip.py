@@ -49,6 +49,8 @@ EXPORTS = [
     "gol_sched_trace", "gol_comm_time", "gol_parse_rule", "gol_set_rule", "gol_get_rule",
     "gol_digest", "gol_digest_window", "gol_digest_async",
     "gol_density_dims", "gol_density", "gol_density_window", "gol_density_async",
+    "gol_bits_row_bytes", "gol_download_bits", "gol_download_bits_window", "gol_download_bits_window_async",
+    "gol_upload_bits", "gol_upload_bits_window",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -118,6 +120,12 @@ def load() -> ctypes.CDLL:
         "gol_density": ([P, i64, i64, ctypes.POINTER(u32), i64], i32),
         "gol_density_window": ([P, i64, i64, i64, i64, i64, i64, ctypes.POINTER(u32), i64], i32),
         "gol_density_async": ([P, i64, i64, ctypes.POINTER(u32), i64], i32),
+        "gol_bits_row_bytes": ([i64], i64),
+        "gol_download_bits": ([P, u8p, i64], i32),
+        "gol_download_bits_window": ([P, i64, i64, i64, i64, u8p, i64], i32),
+        "gol_download_bits_window_async": ([P, i64, i64, i64, i64, u8p, i64], i32),
+        "gol_upload_bits": ([P, u8p, i64], i32),
+        "gol_upload_bits_window": ([P, i64, i64, i64, i64, u8p, i64], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -158,6 +166,14 @@ def density_dims(nrows: int, ncols: int, tile_rows: int, tile_cols: int) -> tupl
     if rc:
         raise GolError(rc, "gol_density_dims: sizes >= 0 and tiles >= 1")
     return tr.value, tc.value
+
+
+def bits_row_bytes(ncols: int) -> int:
+    """Bytes of one packed row of ncols cells: ceil(ncols / 8).  Host-only."""
+    n = load().gol_bits_row_bytes(ncols)
+    if n < 0:
+        raise GolError(n, "gol_bits_row_bytes: ncols >= 0")
+    return n
 
 
 def unique_id() -> bytes:
@@ -323,6 +339,42 @@ class Engine:
                   "gol_download_window_async")
         self._pending.append(out)   # kept alive here until a synchronising call has filled it
         return out
+
+    # ------------------------------------------------------------ packed bits
+    # Rows of ceil(ncols / 8) bytes, MSB first: np.packbits(window, axis=1), a PBM P4 raster.
+    def download_bits(self) -> np.ndarray:
+        """The board as packed rows, packed on the device: np.packbits(download(), axis=1)
+        at an eighth of the transfer.  Rank contexts fill their slab's rows only."""
+        out = np.zeros((self.rows, bits_row_bytes(self.cols)), np.uint8)
+        self._chk(self.lib.gol_download_bits(self._c, _u8(out), out.shape[1]), "gol_download_bits")
+        return out
+
+    def download_bits_window(self, row0: int, col0: int, nrows: int, ncols: int) -> np.ndarray:
+        out = np.zeros((nrows, bits_row_bytes(ncols)), np.uint8)
+        self._chk(self.lib.gol_download_bits_window(self._c, row0, col0, nrows, ncols, _u8(out), out.shape[1]),
+                  "gol_download_bits_window")
+        return out
+
+    def download_bits_window_async(self, row0: int, col0: int, nrows: int, ncols: int) -> np.ndarray:
+        """download_window_async with packed rows: filled by the next synchronising call."""
+        out = np.zeros((nrows, bits_row_bytes(ncols)), np.uint8)
+        self._chk(self.lib.gol_download_bits_window_async(self._c, row0, col0, nrows, ncols, _u8(out), out.shape[1]),
+                  "gol_download_bits_window_async")
+        self._pending.append(out)   # kept alive here until a synchronising call has filled it
+        return out
+
+    def upload_bits(self, arr: np.ndarray):
+        """Packed rows (uint8, shape (rows, ceil(cols / 8))) -> the board; pad bits are ignored."""
+        a = np.ascontiguousarray(arr, dtype=np.uint8)
+        assert a.shape == (self.rows, bits_row_bytes(self.cols)), a.shape
+        self._chk(self.lib.gol_upload_bits(self._c, _u8(a), a.shape[1]), "gol_upload_bits")
+
+    def upload_bits_window(self, row0: int, col0: int, ncols: int, arr: np.ndarray):
+        """Packed rows of an arr.shape[0] × ncols window (the array's width is in bytes)."""
+        a = np.ascontiguousarray(arr, dtype=np.uint8)
+        assert a.ndim == 2 and a.shape[1] == bits_row_bytes(ncols), a.shape
+        self._chk(self.lib.gol_upload_bits_window(self._c, row0, col0, a.shape[0], ncols, _u8(a), a.shape[1]),
+                  "gol_upload_bits_window")
 
     # ------------------------------------------------------------ digest
     def digest(self) -> tuple[int, int]:
