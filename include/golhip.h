@@ -265,6 +265,43 @@ int gol_upload_bits(gol_ctx *ctx, const uint8_t *host, int64_t ld);
 int gol_upload_bits_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
                            const uint8_t *host, int64_t ld);
 
+/* Random fill: a seeded soup at any density, written where the board lives — no
+ * host array, no PCIe.  Counter-based: every cell is a formula of (seed, threshold,
+ * GLOBAL row, GLOBAL column).  All arithmetic mod 2^64, sm = splitmix64's output
+ * function exactly as under gol_digest:
+ *   K        = sm(seed)                                  seed: uint64
+ *   h(r,w,j) = sm( sm(K + r) + 16*w + j )                r = global row, w = global column >> 5, j = 0..15
+ *   plane 2j   (r,w) = low  32 bits of h(r,w,j)
+ *   plane 2j+1 (r,w) = high 32 bits of h(r,w,j)
+ *   X(r,c)   = sum over i = 0..31 of 2^i * bit (c & 31) of plane i (r, c >> 5)      (uniform in [0, 2^32))
+ *   cell (r,c) is live  iff  X(r,c) < T                  T: uint64 threshold, 0 <= T <= 2^32
+ * T = 0 clears the window, T = 2^32 sets every cell, the density is T / 2^32.  A
+ * cell depends on (seed, T, r, c) only: not on the window, the layout, the group
+ * width, tblock_k, the boundary storage, the slab or the rank that writes it, so a
+ * window fill equals the same cells of a whole-board fill and the parts of rank
+ * contexts tile the board's fill with no communication.  Planes below the lowest set
+ * bit of T cannot decide X < T and are not computed: density 1/2 costs half an sm
+ * per 32 cells, a full 32-bit threshold 16.  Not cryptographic.  No reference
+ * counterpart (gol_init_glibc is the reference's start: density 1/3 only).
+ *   gol_fill_threshold      host only: *threshold = llround(density * 2^32) for
+ *                           0 <= density <= 1; GOL_EINVAL for NaN, a value outside
+ *                           [0, 1], a null pointer.
+ *   gol_fill_random_window  behaves as an upload: it writes the current buffer, only
+ *                           the window's cells change, the generation, the rule and
+ *                           the schedule trial stay untouched; it synchronises before
+ *                           and after the write.  A rank context writes the rows it
+ *                           holds.  Cells outside the active region (SERIAL_COMPAT:
+ *                           last row and column) are stored as 0; torus ghost columns
+ *                           are refreshed.  GOL_EINVAL with a message: a window outside
+ *                           the grid, threshold > 2^32.  An empty window is GOL_OK and
+ *                           writes nothing.  Nothing is allocated or staged (see
+ *                           gol_clock_start).
+ *   gol_fill_random         the whole grid; a rank context: its slab. */
+int gol_fill_threshold(double density, uint64_t *threshold);
+int gol_fill_random(gol_ctx *ctx, uint64_t seed, uint64_t threshold);
+int gol_fill_random_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
+                           uint64_t seed, uint64_t threshold);
+
 /* Snapshot text —the body of a `.gol` part file as writeBoardToFile writes it
  * (main.cpp:106-129, main_serial.cpp:74-95; read back by
  * gol_visualization.py:29-33): for every row of the window one "0\t" or "1\t"
@@ -403,7 +440,9 @@ int gol_sched_trace(gol_ctx *ctx, int64_t *ops, int64_t cap, int64_t *n);
  * parts of gol_density* come from the same pool under the same rule: take one
  * map with the same window and tiles beforehand), and
  * the snapshot-text calls and gol_init_glibc return GOL_ESTATE; gol_digest* need
- * their slots allocated by an earlier digest (GOL_ESTATE otherwise). */
+ * their slots allocated by an earlier digest (GOL_ESTATE otherwise).
+ * gol_fill_random[_window] allocates and stages nothing: it works while the probe
+ * runs. */
 int gol_clock_start(gol_ctx *ctx, double max_ms);
 int gol_clock_stop(gol_ctx *ctx, double *mhz, double *span_ms);
 

@@ -31,6 +31,12 @@
 //   --save / --no-save      write snapshots every gap generations
 //                           (default: on for serial, off for mpi/dead as in main.cpp:208)
 //   --seed S                override the srand seed
+//   --soup P                start from a random soup of density P (0 <= P <= 1) in place
+//                           of the mode's glibc init: gol_fill_random with the threshold
+//                           of P (gol_fill_threshold) and seed --seed (default 1), written
+//                           on the device.  Every mode and layout; with --gpus N / --rccl
+//                           every slab fills its own rows (a cell depends on the seed, P
+//                           and its global coordinates only)
 //   --resume NAME --from I  continue the run of NAME.gol from its saved
 //                           iteration I (part files NAME_I_<p>.gol, read back
 //                           on the device); rows/cols/gap/iters default to the
@@ -213,6 +219,7 @@ struct Opts {
     std::string mode = "mpi", layout = "", format = "gol";
     int procs = 1, gpus = 1, k = 1, save = -1;
     long long seed = -1;
+    std::string soup;     // --soup P: the starting density (empty: the mode's glibc init)
     std::string resume;   // --resume NAME: continue the run whose main file is NAME.gol
     int from = -1;        // --from ITER: the saved iteration to continue from
     bool rccl = false, same_device = false;
@@ -284,6 +291,7 @@ int main(int argc, char **argv) {
         else if (a == "--save") o.save = 1;
         else if (a == "--no-save") o.save = 0;
         else if (a == "--seed") o.seed = atoll(next());
+        else if (a == "--soup") o.soup = next();
         else if (a == "--resume") o.resume = next();
         else if (a == "--from") o.from = atoi(next());
         else if (a == "--rccl") o.rccl = true;
@@ -309,6 +317,13 @@ int main(int argc, char **argv) {
     }
     if (o.format != "gol" && o.format != "pbm") die("--format must be gol or pbm");
     const bool pbm = o.format == "pbm";
+    uint64_t soup_threshold = 0;
+    if (!o.soup.empty()) {
+        char *end = nullptr;
+        const double p = strtod(o.soup.c_str(), &end);
+        if (end == o.soup.c_str() || *end || gol_fill_threshold(p, &soup_threshold) != GOL_OK)
+            die("--soup must be a density between 0 and 1");
+    }
     long m_rows = 0, m_cols = 0;
     int m_gap = 0, m_iters = 0, m_parts = 0;
     if (!o.resume.empty()) {
@@ -348,7 +363,7 @@ int main(int argc, char **argv) {
             boundary = GOL_MESH_COMPAT;
             init = GOL_INIT_MESH;
             // the bit layout's device init needs 32-column-aligned mesh blocks
-            if (o.layout.empty() && (cols / m) % 32 != 0) layout = GOL_LAYOUT_BYTE;
+            if (o.layout.empty() && o.soup.empty() && (cols / m) % 32 != 0) layout = GOL_LAYOUT_BYTE;
         }
         save = o.save == 1;   // main.cpp:208 hard-codes save_file = 0
     } else if (o.mode == "serial") {
@@ -424,7 +439,9 @@ int main(int argc, char **argv) {
         if (!o.rule.empty()) check(ctx, gol_set_rule(ctx, birth, survive), "gol_set_rule");   // (-k >= 8: its message)
         // launches are counted on the host (gol_kernel_time without GOL_OPT_KERNEL_TIMING): no event pair
         // per launch inside the timed region
-        if (o.resume.empty()) {
+        if (o.resume.empty() && !o.soup.empty()) {
+            check(ctx, gol_fill_random(ctx, o.seed >= 0 ? (uint64_t)o.seed : 1, soup_threshold), "gol_fill_random");
+        } else if (o.resume.empty()) {
             check(ctx, gol_init_glibc(ctx, init, seed), "gol_init_glibc");
         } else {
             for (int p = 0; p < m_parts; ++p)

@@ -204,4 +204,13 @@ hipError_t launch_put_bits(void *buf, int64_t pitch_bytes, int64_t r0, int64_t r
                            int64_t ncols, int64_t active_cols, const uint32_t *in, int64_t in_pitch_words, int bit_gw,
                            hipStream_t s);
 
+// ---- gol_fill_random*: the counter-based random fill (gol_fill.h, gol_fill.hip) ----
+// launch_put_bits's cells: storage rows [r0, r1) × storage columns [pc0, pc0 + ncols);
+// storage row r0 is GLOBAL row grow0 and storage column pc0 is GLOBAL column lc0.
+// Exactly these cells change: each takes X(r, c) < T of gol_fill.h with K = sm(seed)
+// (T > 2^32 is hipErrorInvalidValue); storage columns >= active_cols are stored as 0.
+hipError_t launch_fill_random(void *buf, int64_t pitch_bytes, int64_t r0, int64_t r1, int64_t grow0, int64_t pc0,
+                              int64_t lc0, int64_t ncols, int64_t active_cols, uint64_t K, uint64_t T, int bit_gw,
+                              hipStream_t s);
+
 } // namespace gol

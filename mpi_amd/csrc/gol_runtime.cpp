@@ -15,6 +15,7 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,6 +31,7 @@
 
 #include "../../include/golhip.h"
 #include "glibc_jump.h"
+#include "gol_fill.h"
 #include "gol_internal.h"
 
 using namespace gol;
@@ -2431,6 +2433,57 @@ int gol_upload_bits_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows
                            int64_t ld) {
     if (!c) return GOL_EINVAL;
     return window_io(c, row0, col0, nrows, ncols, const_cast<uint8_t *>(host), ld, true, true);
+}
+
+// ------------------------------------------------------------------ random fill
+int gol_fill_threshold(double density, uint64_t *threshold) {
+    if (!threshold || !(density >= 0.0 && density <= 1.0)) return GOL_EINVAL;   // (NaN fails both comparisons)
+    *threshold = (uint64_t)llround(density * 4294967296.0);
+    return GOL_OK;
+}
+
+// An upload without a host side (window_io, upload_piece): the window's cells of the
+// current buffer take the formula of gol_fill.h on their GLOBAL coordinates, one
+// launch per slab and column run on the slab's compute stream.  Nothing is allocated
+// or staged, so it runs beside the clock probe.
+int gol_fill_random_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint64_t seed,
+                           uint64_t threshold) {
+    if (!c) return GOL_EINVAL;
+    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
+        return fail(c, GOL_EINVAL, "window outside the grid");
+    if (threshold > kFillFull) return fail(c, GOL_EINVAL, "threshold above 2^32 (the density is threshold / 2^32)");
+    if (nrows == 0 || ncols == 0) return GOL_OK;
+    if (int rc = sync_all(c, nullptr)) return rc;
+    const uint64_t K = fill_key(seed);
+    bool any = false;
+    for (auto &s : c->slabs) {
+        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
+        if (r1 <= r0) continue;
+        any = true;
+        const int64_t srow = c->hk + (r0 - s.row0), nr = r1 - r0;
+        HIPCHK(c, hipSetDevice(s.device));
+        tr_op(c, TR_WRITE, s.comp, nullptr, s.index, c->cur, srow, srow + nr);
+        int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
+            HIPCHK(c, launch_fill_random(s.buf[c->cur], c->pitch_bytes, srow, srow + nr, r0, pc, lc, n, c->active_cols,
+                                         K, threshold, c->layout == GOL_LAYOUT_BIT ? c->gw : 0, s.comp));
+            return GOL_OK;
+        });
+        if (!rc) rc = wrap_rows(c, s, c->cur, srow, srow + nr, s.comp);
+        if (!rc) rc = enforce_inactive(c, s, c->cur);
+        if (rc) return rc;
+        HIPCHK(c, tr_ssync(c, s.comp));
+    }
+    if (!any && c->transport != GOL_XPORT_RCCL) return fail(c, GOL_EINVAL, "window holds no local rows");
+    return GOL_OK;
+}
+
+int gol_fill_random(gol_ctx *c, uint64_t seed, uint64_t threshold) {
+    if (!c) return GOL_EINVAL;
+    if (c->transport == GOL_XPORT_RCCL) {
+        const Slab &s = c->slabs[0];
+        return gol_fill_random_window(c, s.row0, 0, s.H, c->cols, seed, threshold);
+    }
+    return gol_fill_random_window(c, 0, 0, c->rows, c->cols, seed, threshold);
 }
 
 int64_t gol_text_bytes(int64_t nrows, int64_t ncols) {

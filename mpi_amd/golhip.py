@@ -51,6 +51,7 @@ EXPORTS = [
     "gol_density_dims", "gol_density", "gol_density_window", "gol_density_async",
     "gol_bits_row_bytes", "gol_download_bits", "gol_download_bits_window", "gol_download_bits_window_async",
     "gol_upload_bits", "gol_upload_bits_window",
+    "gol_fill_threshold", "gol_fill_random", "gol_fill_random_window",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -126,6 +127,9 @@ def load() -> ctypes.CDLL:
         "gol_download_bits_window_async": ([P, i64, i64, i64, i64, u8p, i64], i32),
         "gol_upload_bits": ([P, u8p, i64], i32),
         "gol_upload_bits_window": ([P, i64, i64, i64, i64, u8p, i64], i32),
+        "gol_fill_threshold": ([ctypes.c_double, ctypes.POINTER(ctypes.c_uint64)], i32),
+        "gol_fill_random": ([P, ctypes.c_uint64, ctypes.c_uint64], i32),
+        "gol_fill_random_window": ([P, i64, i64, i64, i64, ctypes.c_uint64, ctypes.c_uint64], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -174,6 +178,15 @@ def bits_row_bytes(ncols: int) -> int:
     if n < 0:
         raise GolError(n, "gol_bits_row_bytes: ncols >= 0")
     return n
+
+
+def fill_threshold(p: float) -> int:
+    """The threshold of density p for Engine.fill_random: round(p * 2^32), 0 <= p <= 1.  Host-only."""
+    t = ctypes.c_uint64()
+    rc = load().gol_fill_threshold(p, ctypes.byref(t))
+    if rc:
+        raise GolError(rc, f"gol_fill_threshold: a density in [0, 1], not {p!r}")
+    return t.value
 
 
 def unique_id() -> bytes:
@@ -375,6 +388,21 @@ class Engine:
         assert a.ndim == 2 and a.shape[1] == bits_row_bytes(ncols), a.shape
         self._chk(self.lib.gol_upload_bits_window(self._c, row0, col0, a.shape[0], ncols, _u8(a), a.shape[1]),
                   "gol_upload_bits_window")
+
+    # ------------------------------------------------------------ random fill
+    def fill_random(self, density: float = 0.5, seed: int = 0, window: tuple[int, int, int, int] | None = None,
+                    threshold: int | None = None):
+        """A seeded soup written on the device: cell (r, c) is live iff X(seed, r, c) < threshold
+        (include/golhip.h, tests/fill_ref.py), threshold = fill_threshold(density) unless given
+        (0 .. 2^32).  window = (row0, col0, nrows, ncols): only those cells change, and they equal
+        the same cells of a whole-board fill.  The generation and the rule stay as they are.
+        Rank contexts write the rows they hold.  Synchronises."""
+        t = fill_threshold(density) if threshold is None else threshold
+        if window is None:
+            self._chk(self.lib.gol_fill_random(self._c, seed, t), "gol_fill_random")
+        else:
+            self._chk(self.lib.gol_fill_random_window(self._c, *window, seed, t), "gol_fill_random_window")
+        self._pending = []
 
     # ------------------------------------------------------------ digest
     def digest(self) -> tuple[int, int]:
