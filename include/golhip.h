@@ -302,6 +302,50 @@ int gol_fill_random(gol_ctx *ctx, uint64_t seed, uint64_t threshold);
 int gol_fill_random_window(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
                            uint64_t seed, uint64_t threshold);
 
+/* Board-to-board copies, on the device: the cells of a window of `src` are merged
+ * into a window of the same size of `dst`.  In LOGICAL cells (global coordinates,
+ * as gol_download shows them): for 0 <= i < nrows and 0 <= j < ncols, cell
+ * (drow0 + i, dcol0 + j) of dst becomes op(its old value, cell (srow0 + i, scol0 + j)
+ * of src); no other cell of dst changes and src does not change.  The two contexts
+ * need not agree in anything: layout and group width, tblock_k, boundary storage
+ * (torus ghost columns, MESH_COMPAT's reversed blocks: ghost columns are never
+ * copied as cells), slab count, transport and size are each side's own; one kernel
+ * goes from storage to storage in one pass, at any column shift.
+ *   gol_copy_window  behaves as an upload into dst: it writes dst's current buffer;
+ *                    the generation, rule, options and schedule trial of both
+ *                    contexts stay as they are; cells outside dst's active region
+ *                    (SERIAL_COMPAT: last row and column) are stored as 0 under every
+ *                    op; dst's torus ghost columns are refreshed.  It synchronises
+ *                    both contexts before the write and dst after it (pending async
+ *                    windows, digests and maps of both are delivered).  Nothing is
+ *                    allocated or staged (see gol_clock_start).
+ *                    Rank contexts: the rows of the destination window that dst
+ *                    holds are written, the others are skipped; every written row's
+ *                    source row must be held by src.
+ *                    src == dst is allowed when the two rectangles are disjoint (a
+ *                    pattern tiled within one board).
+ *                    Errors are found before anything is written (dst is unchanged),
+ *                    the message goes to gol_last_error(dst).  GOL_EINVAL: a null
+ *                    context (no message); a window outside either grid; negative
+ *                    sizes; an unknown op; a source row that src does not hold; a
+ *                    destination window with no local rows unless dst is a rank
+ *                    context; overlapping rectangles in one context.
+ *                    GOL_EUNSUPPORTED: a row piece whose source slab and destination
+ *                    slab live on different HIP devices — this version copies
+ *                    within a device (two contexts of the same n_gpus and rows line
+ *                    up slab for slab).  An empty window is GOL_OK and writes nothing.
+ *   gol_copy         the whole board, REPLACE; GOL_EINVAL unless rows and cols match.
+ *                    Rank contexts: the rows dst holds.
+ * There is no _async form in this version: ordering the streams of two contexts
+ * against each other is a piece of work of its own.  No reference counterpart. */
+#define GOL_COPY_REPLACE 0   /* dst = src            */
+#define GOL_COPY_OR      1   /* dst = dst | src      */
+#define GOL_COPY_XOR     2   /* dst = dst ^ src      */
+int gol_copy_window(gol_ctx *dst, int64_t drow0, int64_t dcol0,
+                    gol_ctx *src, int64_t srow0, int64_t scol0,
+                    int64_t nrows, int64_t ncols, int op);
+int gol_copy(gol_ctx *dst, gol_ctx *src);
+
 /* Snapshot text —the body of a `.gol` part file as writeBoardToFile writes it
  * (main.cpp:106-129, main_serial.cpp:74-95; read back by
  * gol_visualization.py:29-33): for every row of the window one "0\t" or "1\t"
@@ -442,7 +486,7 @@ int gol_sched_trace(gol_ctx *ctx, int64_t *ops, int64_t cap, int64_t *n);
  * the snapshot-text calls and gol_init_glibc return GOL_ESTATE; gol_digest* need
  * their slots allocated by an earlier digest (GOL_ESTATE otherwise).
  * gol_fill_random[_window] allocates and stages nothing: it works while the probe
- * runs. */
+ * runs.  So does gol_copy[_window], with the probe on either context. */
 int gol_clock_start(gol_ctx *ctx, double max_ms);
 int gol_clock_stop(gol_ctx *ctx, double *mhz, double *span_ms);
 

@@ -213,4 +213,16 @@ hipError_t launch_fill_random(void *buf, int64_t pitch_bytes, int64_t r0, int64_
                               int64_t lc0, int64_t ncols, int64_t active_cols, uint64_t K, uint64_t T, int bit_gw,
                               hipStream_t s);
 
+// ---- gol_copy_window / gol_copy: board-to-board copies (gol_copy.h, gol_copy.hip) ----
+// nrows storage rows from sr0 of `src` (pitch src_pitch_bytes, storage form src_gw) ×
+// its storage columns [spc0, spc0 + ncols) are merged into the rows from dr0 of `dst`
+// × its storage columns [dpc0, dpc0 + ncols) under op (GOL_COPY_*); *_gw: 0 = byte
+// layout, else the bit layout's group width.  Exactly these cells of dst change;
+// destination storage columns >= active_cols are stored as 0.  Of src only the units
+// that hold cells of the run are read.  src and dst may be one buffer when the two
+// rectangles are disjoint.  The two buffers live on the device of stream s.
+hipError_t launch_copy_cells(const void *src, int64_t src_pitch_bytes, int64_t sr0, int64_t spc0, int src_gw, void *dst,
+                             int64_t dst_pitch_bytes, int64_t dr0, int64_t dpc0, int dst_gw, int64_t nrows,
+                             int64_t ncols, int64_t active_cols, int op, hipStream_t s);
+
 } // namespace gol

@@ -2486,6 +2486,109 @@ int gol_fill_random(gol_ctx *c, uint64_t seed, uint64_t threshold) {
     return gol_fill_random_window(c, 0, 0, c->rows, c->cols, seed, threshold);
 }
 
+// ------------------------------------------------------------------ board-to-board copy
+// An upload whose host side is another context (gol_fill_random_window's shape): per
+// destination slab the rows of the window it holds, cut by the source slabs; per row
+// piece the for_col_runs runs of both contexts, paired in window-relative columns and
+// clipped to each other, one launch_copy_cells each on the DESTINATION slab's compute
+// stream.  Everything is checked before anything is written; nothing is allocated or
+// staged, so it runs beside the clock probe of either context.
+int gol_copy_window(gol_ctx *d, int64_t drow0, int64_t dcol0, gol_ctx *c, int64_t srow0, int64_t scol0, int64_t nrows,
+                    int64_t ncols, int op) {
+    if (!d || !c) return GOL_EINVAL;
+    if (nrows < 0 || ncols < 0) return fail(d, GOL_EINVAL, "negative window size");
+    if (drow0 < 0 || dcol0 < 0 || drow0 + nrows > d->rows || dcol0 + ncols > d->cols)
+        return fail(d, GOL_EINVAL, "destination window outside the grid");
+    if (srow0 < 0 || scol0 < 0 || srow0 + nrows > c->rows || scol0 + ncols > c->cols)
+        return fail(d, GOL_EINVAL, "source window outside the grid");
+    if (op != GOL_COPY_REPLACE && op != GOL_COPY_OR && op != GOL_COPY_XOR)
+        return fail(d, GOL_EINVAL, "unknown copy op %d", op);
+    if (nrows == 0 || ncols == 0) return GOL_OK;
+    if (c == d && drow0 < srow0 + nrows && srow0 < drow0 + nrows && dcol0 < scol0 + ncols && scol0 < dcol0 + ncols)
+        return fail(d, GOL_EINVAL, "source and destination rectangles of one context overlap");
+    // the row pieces: rows [r0, r1) of the destination window held by destination slab di,
+    // whose source rows r + (srow0 - drow0) are held by source slab si
+    struct Piece {
+        size_t di, si;
+        int64_t r0, r1;
+    };
+    std::vector<Piece> pieces;
+    const int64_t shift = srow0 - drow0;
+    bool any = false;
+    for (size_t di = 0; di < d->slabs.size(); ++di) {
+        const Slab &ds = d->slabs[di];
+        const int64_t a = std::max(drow0, ds.row0), b = std::min(drow0 + nrows, ds.row0 + ds.H);
+        if (b <= a) continue;
+        any = true;
+        int64_t held = 0;
+        for (size_t si = 0; si < c->slabs.size(); ++si) {
+            const Slab &ss = c->slabs[si];
+            const int64_t r0 = std::max(a, ss.row0 - shift), r1 = std::min(b, ss.row0 + ss.H - shift);
+            if (r1 <= r0) continue;
+            held += r1 - r0;
+            if (ss.device != ds.device)
+                return fail(d, GOL_EUNSUPPORTED,
+                            "source rows [%lld, %lld) live on device %d, their destination rows on device %d: this "
+                            "version copies within a device",
+                            (long long)(r0 + shift), (long long)(r1 + shift), ss.device, ds.device);
+            pieces.push_back({di, si, r0, r1});
+        }
+        if (held != b - a)
+            return fail(d, GOL_EINVAL, "the source context does not hold every source row of destination rows [%lld, %lld)",
+                        (long long)a, (long long)b);
+    }
+    if (!any && d->transport != GOL_XPORT_RCCL) return fail(d, GOL_EINVAL, "window holds no local rows");
+    if (int rc = sync_all(c, nullptr)) return c == d ? rc : fail(d, rc, "synchronising the source: %s", c->err.c_str());
+    if (c != d)
+        if (int rc = sync_all(d, nullptr)) return rc;
+    const int sgw = c->layout == GOL_LAYOUT_BIT ? c->gw : 0, dgw = d->layout == GOL_LAYOUT_BIT ? d->gw : 0;
+    for (size_t di = 0; di < d->slabs.size(); ++di) {
+        Slab &ds = d->slabs[di];
+        int64_t lo = -1, hi = -1;   // destination rows of this slab's pieces
+        HIPCHK(d, hipSetDevice(ds.device));
+        for (const Piece &p : pieces) {
+            if (p.di != di) continue;
+            const Slab &ss = c->slabs[p.si];
+            const int64_t nr = p.r1 - p.r0;
+            const int64_t drow = d->hk + (p.r0 - ds.row0), srow = c->hk + (p.r0 + shift - ss.row0);
+            lo = lo < 0 ? p.r0 : std::min(lo, p.r0);
+            hi = std::max(hi, p.r1);
+            tr_op(c, TR_READ, ds.comp, nullptr, ss.index, c->cur, srow, srow + nr);
+            tr_op(d, TR_WRITE, ds.comp, nullptr, ds.index, d->cur, drow, drow + nr);
+            int rc = for_col_runs(d, dcol0, ncols, [&](int64_t dlc, int64_t dpc, int64_t dn) -> int {
+                return for_col_runs(c, scol0 + (dlc - dcol0), dn, [&](int64_t slc, int64_t spc, int64_t n) -> int {
+                    const int64_t off = slc - (scol0 + (dlc - dcol0));   // of this source run inside the destination run
+                    HIPCHK(d, launch_copy_cells(ss.buf[c->cur], c->pitch_bytes, srow, spc, sgw, ds.buf[d->cur],
+                                                d->pitch_bytes, drow, dpc + off, dgw, nr, n, d->active_cols, op,
+                                                ds.comp));
+                    return GOL_OK;
+                });
+            });
+            if (rc) return rc;
+        }
+        if (lo < 0) continue;
+        const int64_t w0 = d->hk + (lo - ds.row0), w1 = d->hk + (hi - ds.row0);
+        int rc = wrap_rows(d, ds, d->cur, w0, w1, ds.comp);
+        if (!rc) rc = enforce_inactive(d, ds, d->cur);
+        if (rc) return rc;
+        HIPCHK(d, tr_ssync(d, ds.comp));
+        if (c != d) tr_op(c, TR_STREAM_SYNC, ds.comp, nullptr);   // the source's trace: its reads are complete
+    }
+    return GOL_OK;
+}
+
+int gol_copy(gol_ctx *d, gol_ctx *c) {
+    if (!d || !c) return GOL_EINVAL;
+    if (d->rows != c->rows || d->cols != c->cols)
+        return fail(d, GOL_EINVAL, "gol_copy needs boards of one size (%lld x %lld <- %lld x %lld)", (long long)d->rows,
+                    (long long)d->cols, (long long)c->rows, (long long)c->cols);
+    if (d->transport == GOL_XPORT_RCCL) {
+        const Slab &s = d->slabs[0];
+        return gol_copy_window(d, s.row0, 0, c, s.row0, 0, s.H, d->cols, GOL_COPY_REPLACE);
+    }
+    return gol_copy_window(d, 0, 0, c, 0, 0, d->rows, d->cols, GOL_COPY_REPLACE);
+}
+
 int64_t gol_text_bytes(int64_t nrows, int64_t ncols) {
     if (nrows < 0 || ncols < 0) return GOL_EINVAL;
     return nrows * (2 * ncols + 1);

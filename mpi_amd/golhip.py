@@ -21,6 +21,7 @@ import numpy as np
 LAYOUT = {"byte": 0, "bit": 1}
 BOUNDARY = {"dead": 0, "serial_compat": 1, "mesh_compat": 2, "torus": 3}
 INIT = {"stream": 0, "serial": 1, "mesh": 2}
+COPY_OPS = {"replace": 0, "or": 1, "xor": 2}   # GOL_COPY_*
 SERIAL_SEED = 1804289383
 
 OPT_CHUNK_ROWS = 1
@@ -52,6 +53,7 @@ EXPORTS = [
     "gol_bits_row_bytes", "gol_download_bits", "gol_download_bits_window", "gol_download_bits_window_async",
     "gol_upload_bits", "gol_upload_bits_window",
     "gol_fill_threshold", "gol_fill_random", "gol_fill_random_window",
+    "gol_copy_window", "gol_copy",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,6 +132,8 @@ def load() -> ctypes.CDLL:
         "gol_fill_threshold": ([ctypes.c_double, ctypes.POINTER(ctypes.c_uint64)], i32),
         "gol_fill_random": ([P, ctypes.c_uint64, ctypes.c_uint64], i32),
         "gol_fill_random_window": ([P, i64, i64, i64, i64, ctypes.c_uint64, ctypes.c_uint64], i32),
+        "gol_copy_window": ([P, i64, i64, P, i64, i64, i64, i64, i32], i32),
+        "gol_copy": ([P, P], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -251,6 +255,8 @@ class Engine:
         self._pending = []   # arrays the library fills at the next synchronising call
         self.rows, self.cols = rows, cols
         self.layout, self.boundary, self.tblock_k = layout, boundary, tblock_k
+        self.mesh_m, self.n_gpus = mesh_m, n_gpus
+        self._rank_ctx = rank is not None
         self._c = ctypes.c_void_p()
         if rank is None:
             rc = self.lib.gol_create(ctypes.byref(self._c), rows, cols, n_gpus, LAYOUT[layout],
@@ -404,6 +410,65 @@ class Engine:
             self._chk(self.lib.gol_fill_random_window(self._c, *window, seed, t), "gol_fill_random_window")
         self._pending = []
 
+    # ------------------------------------------------------------ board-to-board copy
+    def copy_from(self, src: "Engine", window: tuple[int, int, int, int] | None = None,
+                  at: tuple[int, int] = (0, 0), op: str = "replace"):
+        """Cells of `src` merged into this board on the device (gol_copy_window): window =
+        (row0, col0, nrows, ncols) of src (default its whole board) lands with its corner at
+        `at`; op = "replace", "or" or "xor".  The two engines may differ in layout, tblock_k,
+        boundary, slab count and size; the generation and rule of both stay as they are.
+        src may be this engine when the two rectangles are disjoint.  Rank contexts write
+        the rows they hold, whose source rows src must hold.  Synchronises both engines."""
+        if op not in COPY_OPS:
+            raise ValueError(f"copy_from: op must be one of {sorted(COPY_OPS)}")
+        row0, col0, nrows, ncols = (0, 0, src.rows, src.cols) if window is None else window
+        self._chk(self.lib.gol_copy_window(self._c, at[0], at[1], src._c, row0, col0, nrows, ncols, COPY_OPS[op]),
+                  "gol_copy_window")
+        self._pending = []
+        src._pending = []
+
+    def clone(self, **overrides) -> "Engine":
+        """A new single-process Engine of the same rows, cols, boundary, mesh_m, layout,
+        tblock_k, n_gpus and rule — except where overridden — with this board copied in on
+        the device.  Its generation starts at 0.  GolError where the target cannot run the
+        rule (set_rule's limits).  A rank context cannot be cloned this way (ValueError)."""
+        if self._rank_ctx:
+            raise ValueError("clone: a rank context holds one slab of the board; create the target ranks and copy_from")
+        kw = dict(n_gpus=self.n_gpus, layout=self.layout, boundary=self.boundary, mesh_m=self.mesh_m,
+                  tblock_k=self.tblock_k, rule=self.rule)
+        rows, cols = overrides.pop("rows", self.rows), overrides.pop("cols", self.cols)
+        kw.update(overrides)
+        e = Engine(rows, cols, **kw)
+        try:
+            e.copy_from(self, (0, 0, min(rows, self.rows), min(cols, self.cols)))
+        except Exception:
+            e.close()
+            raise
+        return e
+
+    def period(self, limit: int, batch: int = 64):
+        """The smallest p in 1 .. limit at which the board returns to its present state, or
+        None: the exact period that find_repeat cannot give.  A clone of the board is
+        stepped one generation at a time with a digest_async after each, one sync per
+        `batch` generations, and compared against this board's digest; this engine does
+        not move.  (Equal digests: equal boards up to the digest's collision odds.)"""
+        if limit < 1 or batch < 1 or batch > 1024:
+            raise ValueError("period: limit >= 1 and 1 <= batch <= 1024")
+        want = self.digest()
+        with self.clone() as e:
+            p = 0
+            while p < limit:
+                outs = []
+                for _ in range(min(batch, limit - p)):
+                    e.step(1)
+                    p += 1
+                    outs.append((p, e.digest_async()))
+                e.sync()
+                for g, o in outs:
+                    if (int(o[0]), int(o[1])) == want:
+                        return g
+        return None
+
     # ------------------------------------------------------------ digest
     def digest(self) -> tuple[int, int]:
         """128-bit digest of the logical board (two 64-bit lanes), computed on the device:
@@ -440,7 +505,8 @@ class Engine:
         (generation_first_seen, generation_repeated) for the first digest seen before
         (the digest of the current generation is included), or None once max_generations
         more generations have been stepped (whole multiples of `every`).
-        The distance is a multiple of `every`, and the board's true period divides it;
+        The distance is a multiple of `every`, and the board's true period divides it
+        (`period` finds the exact one);
         generation_first_seen is the first CHECKED generation inside the cycle.  The
         engine is left at the end of the batch in which the repeat was found (see
         `generation`), not at generation_repeated.  A rank context compares its own slab
