@@ -152,6 +152,18 @@ extern "C" {
                                    GOL_EUNSUPPORTED).  Setting it synchronises the context.  RCCL mode:
                                    local state, results do not depend on it */
 
+#define GOL_OPT_RULE_COMPILED 17 /* 1 (default): a rule on the list of gol_compiled_rule runs the kernel
+                                    compiled for it, at a depth that has one; 0: it runs the rule-generic
+                                    kernel like any other rule.  GOL_OPT_RULE_KERNEL = 1 takes precedence
+                                    (everything generic).  Values other than 0 and 1 are GOL_EINVAL.
+                                    Setting it synchronises the context.  RCCL mode: local state,
+                                    results do not depend on it */
+
+/* gol_rule_path: which kernels the next gol_step launches for the context's rule. */
+#define GOL_RULE_PATH_TUNED 0    /* B3/S23 on the kernels tuned for it */
+#define GOL_RULE_PATH_GENERIC 1  /* the rule-generic kernel (the rule is a launch argument) */
+#define GOL_RULE_PATH_COMPILED 2 /* the kernel compiled for this rule (the rule is its immediates) */
+
 typedef struct gol_ctx gol_ctx;
 
 /* Single process.  The grid is cut into n_gpus row slabs; slab s lives on HIP
@@ -179,8 +191,9 @@ int gol_get_option(gol_ctx *ctx, int option, int64_t *value);
  * dead cell with n live neighbours, out of 8, is born; bit n of `survive`: a live
  * cell with n live neighbours stays alive.  A new context runs B3/S23
  * (birth = 1<<3, survive = (1<<2)|(1<<3)), the one rule the reference knows
- * (main.cpp:79-91), on the kernels tuned for it; any other rule runs the
- * rule-generic kernel.
+ * (main.cpp:79-91), on the kernels tuned for it; a rule on the list of
+ * gol_compiled_rule runs a kernel compiled for it (GOL_OPT_RULE_COMPILED); any
+ * other rule runs the rule-generic kernel.  All three compute the same boards.
  *   gol_parse_rule  (host only, no context) "B36/S23" or "S23/B36" in either letter
  *                   case, or the legacy survive/birth form "23/3"; a digit list may
  *                   be empty ("B2/S"); digits are 0..8, each at most once.  Anything
@@ -199,10 +212,22 @@ int gol_get_option(gol_ctx *ctx, int option, int64_t *value);
  *                   Setting B3/S23 itself is GOL_OK on every context.
  *                   RCCL mode: the rule is local state, so the call is COLLECTIVE:
  *                   set it alike on every rank, between the same two steps.
- *   gol_get_rule    the rule in force. */
+ *   gol_get_rule    the rule in force.
+ *   gol_compiled_rule (host only, no context) entry `index` (0, 1, ...) of the list of
+ *                   rules with kernels of their own: its masks and its usual name
+ *                   (a static string).  Any output may be null.  An index outside
+ *                   the list is GOL_EINVAL, so counting up to the first GOL_EINVAL
+ *                   enumerates it.  B3/S23 is not on it.
+ *   gol_rule_path   what the next gol_step of this context launches for its rule, one
+ *                   of GOL_RULE_PATH_*: the rule in force, GOL_OPT_RULE_KERNEL and
+ *                   GOL_OPT_RULE_COMPILED decide it, in that order (tuned, else
+ *                   compiled, else generic).  A short last block of a step may run
+ *                   a shallower kernel of the same or the generic path. */
 int gol_parse_rule(const char *text, uint32_t *birth, uint32_t *survive);
 int gol_set_rule(gol_ctx *ctx, uint32_t birth, uint32_t survive);
 int gol_get_rule(gol_ctx *ctx, uint32_t *birth, uint32_t *survive);
+int gol_compiled_rule(int index, uint32_t *birth, uint32_t *survive, const char **name);
+int gol_rule_path(gol_ctx *ctx, int *path);
 
 /* On-device glibc-rand initialisation with jump-ahead, bit-identical to the
  * reference's initializeBoard (main.cpp:68-77, main_serial.cpp:34-43). */

@@ -28,6 +28,10 @@
 //                           --mode dead|torus, --layout bit and -k 1..7 (the mpi and
 //                           serial modes reproduce the reference, which knows one
 //                           rule).  Snapshots and timing files as without it
+//   --rule-kernel auto|generic   auto (default): a rule with a kernel compiled for it
+//                           (gol_compiled_rule) runs that kernel; generic: every --rule
+//                           runs the rule-generic kernel (GOL_OPT_RULE_COMPILED 0).
+//                           The boards are the same
 //   --save / --no-save      write snapshots every gap generations
 //                           (default: on for serial, off for mpi/dead as in main.cpp:208)
 //   --seed S                override the srand seed
@@ -225,6 +229,7 @@ struct Opts {
     bool rccl = false, same_device = false;
     std::string rccl_lib;
     std::string rule;     // --rule: B/S notation (empty: B3/S23 on the tuned kernels)
+    std::string rule_kernel = "auto";   // --rule-kernel: auto | generic
     bool digest = false;  // --digest: print the board's digest at every snapshot point and at the end
     int64_t tile_rows = 0, tile_cols = 0;   // --density T[xU] (0: no map)
 };
@@ -287,6 +292,7 @@ int main(int argc, char **argv) {
         else if (a == "--layout") o.layout = next();
         else if (a == "-k") o.k = atoi(next());
         else if (a == "--rule") o.rule = next();
+        else if (a == "--rule-kernel") o.rule_kernel = next();
         else if (a == "--format") o.format = next();
         else if (a == "--save") o.save = 1;
         else if (a == "--no-save") o.save = 0;
@@ -381,6 +387,7 @@ int main(int argc, char **argv) {
         die("--mode must be mpi, serial, dead or torus");
     }
     uint32_t birth = 0, survive = 0;
+    if (o.rule_kernel != "auto" && o.rule_kernel != "generic") die("--rule-kernel must be auto or generic");
     if (!o.rule.empty()) {
         if (gol_parse_rule(o.rule.c_str(), &birth, &survive) != GOL_OK)
             die("--rule must be in B/S notation, such as B36/S23, S23/B36 or 23/3");
@@ -437,6 +444,7 @@ int main(int argc, char **argv) {
             check(nullptr, gol_create(&ctx, rows, cols, o.gpus, layout, boundary, m, o.k), "gol_create");
         rk[i].ctx = ctx;
         if (!o.rule.empty()) check(ctx, gol_set_rule(ctx, birth, survive), "gol_set_rule");   // (-k >= 8: its message)
+        if (o.rule_kernel == "generic") check(ctx, gol_set_option(ctx, GOL_OPT_RULE_COMPILED, 0), "GOL_OPT_RULE_COMPILED");
         // launches are counted on the host (gol_kernel_time without GOL_OPT_KERNEL_TIMING): no event pair
         // per launch inside the timed region
         if (o.resume.empty() && !o.soup.empty()) {

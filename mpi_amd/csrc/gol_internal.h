@@ -89,6 +89,11 @@ hipError_t launch_bit_pipe(const StencilArgs &a, int gens, hipStream_t s);
 // pipeline, gens = 1..7 on 2-word groups.  A launch it cannot serve is an error.
 bool bit_rule_supported(int gens, int gw);
 hipError_t launch_bit_rule(const StencilArgs &a, int gens, const RuleMasks &rule, hipStream_t s);
+// Bit layout, a rule of GOL_COMPILED_RULES (gol_rule.h) by its index: the same
+// pipeline with the rule compiled into the stage's immediates.  A depth or an
+// index without a compiled kernel is an error (the caller asks first).
+bool bit_crule_supported(int gens, int gw, int rule_index);
+hipError_t launch_bit_crule(const StencilArgs &a, int gens, int rule_index, hipStream_t s);
 // Byte layout, `gens` generations fused (1 <= gens <= 8), 16 cells per lane.
 hipError_t launch_byte_pipe(const StencilArgs &a, int gens, hipStream_t s);
 // Byte layout with the bit-sliced core (bytebit_pipe_kernel): byte-per-cell in

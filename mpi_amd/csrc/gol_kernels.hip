@@ -28,6 +28,8 @@
 //                 strip handing rows through LDS (the headline at k = 16).
 //  * bit layout, life-like rules other than B3/S23 (k <= 7): bit_rule_kernel, the
 //                 bit pipeline with the table-driven stage of gol_rule.h (end of file).
+//  * bit layout, the rules of GOL_COMPILED_RULES (k <= 7): bit_crule_kernel, the same
+//                 pipeline with the rule as the stage's immediates (very end of file).
 #include "gol_internal.h"
 #include "gol_digest.h"
 #include "gol_density.h"
@@ -438,7 +440,7 @@ __device__ __forceinline__ uint32_t life_bits_full(uint32_t a0, uint32_t a1, uin
 // The rule stage of the register pipeline below is a functor, apply<EDGE>(the
 // life_bits arguments).  This one is B3/S23 as the tuned truth tables above: no
 // state, so the instantiations that name it compile to what they did when the
-// two calls stood in bit_phase.  (The other one: RuleStage, at the end of the file.)
+// two calls stood in bit_phase.  (The others: RuleStage and ConstRuleStage, at the end of the file.)
 struct LifeStage {
     template <bool EDGE>
     __device__ __forceinline__ uint32_t apply(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
@@ -3333,6 +3335,78 @@ hipError_t launch_density(const void *buf, int64_t pitch_bytes, int64_t r0, int6
                        nrows, trow_off, pc0, lc0, ncols, col0, tile_rows, tile_cols, seg_rows, q0, nunits, part, ti_base,
                        ntr, tcols);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- compiled rules
+// The rules of GOL_COMPILED_RULES (gol_rule.h) on kernels of their own:
+// bit_rule_kernel's body with the rule as template arguments, so the stage is
+// rule_const_bits' immediates: no fifth argument, no table, no coefficient
+// SGPRs.  Rings, chains and waves per depth are bit_rule_fn's.  Emitted behind
+// every other kernel so that none of them moves.
+template <uint32_t BIRTH, uint32_t SURVIVE>
+struct ConstRuleStage {
+    template <bool EDGE>
+    __device__ __forceinline__ uint32_t apply(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0,
+                                              uint32_t c1, uint32_t alive, uint32_t mask) const {
+        return rule_const_bits<BIRTH, SURVIVE, EDGE>(a0, a1, b0, b1, c0, c1, alive, mask);
+    }
+};
+
+template <int K, int NCH, int RING, int WPE, uint32_t BIRTH, uint32_t SURVIVE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
+void bit_crule_kernel(StencilArgs a, Sched q, int nstrips, int nblocks) {
+    constexpr int V = 2, G = 2;
+    for_each_item(a, q, nstrips, nblocks, [&](int strip, int r0, int r1) {
+        Strip<V> st;
+        st.setup(a, K, strip, r0, r1, 0u);
+        const ConstRuleStage<BIRTH, SURVIVE> stage;
+        constexpr int CL = (K + NCH - 1) / NCH;
+        constexpr int M = 2 * K + (K - 1) / CL;   // as bit_pipe_kernel: the chunk's light cone
+        const uint32_t all = st.mask[0] & st.mask[1];
+        const bool full = __builtin_amdgcn_ballot_w64(all != 0xffffffffu) == 0ull;
+        if (full && st.R0 - M >= a.row_lo && st.R1 + M <= a.row_hi) bit_run<V, K, CL, RING, 0, false, G>(st, a, stage);
+        else bit_run<V, K, CL, RING, 0, true, G>(st, a, stage);
+    });
+}
+
+template <uint32_t BIRTH, uint32_t SURVIVE>
+static const void *bit_crule_fn_of(int gens) {
+    switch (gens) {
+    case 1: return (const void *)&bit_crule_kernel<1, 1, 18, 4, BIRTH, SURVIVE>;
+    case 2: return (const void *)&bit_crule_kernel<2, 1, 24, 4, BIRTH, SURVIVE>;
+    case 3: return (const void *)&bit_crule_kernel<3, 1, 6, 4, BIRTH, SURVIVE>;
+    case 4: return (const void *)&bit_crule_kernel<4, 1, 6, 4, BIRTH, SURVIVE>;
+    case 5: return (const void *)&bit_crule_kernel<5, 2, 6, 4, BIRTH, SURVIVE>;
+    case 6: return (const void *)&bit_crule_kernel<6, 2, 6, 4, BIRTH, SURVIVE>;
+    case 7: return (const void *)&bit_crule_kernel<7, 2, 6, 4, BIRTH, SURVIVE>;
+    default: return nullptr;
+    }
+}
+
+static const void *bit_crule_fn(int gens, int rule_index) {
+    using Fn = const void *(*)(int);
+#define GOL_CRULE_FN(name, b, s) &bit_crule_fn_of<rule_mask(b), rule_mask(s)>,
+    static const Fn table[] = {GOL_COMPILED_RULES(GOL_CRULE_FN)};
+#undef GOL_CRULE_FN
+    static_assert(sizeof(table) / sizeof(table[0]) == kCompiledRuleCount, "one entry per listed rule");
+    return rule_index >= 0 && rule_index < kCompiledRuleCount ? table[rule_index](gens) : nullptr;
+}
+
+bool bit_crule_supported(int gens, int gw, int rule_index) {
+    return gw == 2 && bit_crule_fn(gens, rule_index) != nullptr;
+}
+
+hipError_t launch_bit_crule(const StencilArgs &a, int gens, int rule_index, hipStream_t s) {
+    if (a.out_r1 <= a.out_r0) return hipSuccess;
+    const void *fn = a.gw == 2 ? bit_crule_fn(gens, rule_index) : nullptr;
+    if (!fn) return hipErrorInvalidValue;   // no fall-back: the caller asks bit_crule_supported first
+    int waves = 0, ns = 0;
+    Sched q = plan_items(a, gens, 2, true, fn, waves, ns);
+    if (q.nitems <= 0) return hipSuccess;
+    int nb = (waves + 3) / 4;
+    StencilArgs aa = a;
+    void *args[] = {&aa, &q, &ns, &nb};
+    return hipLaunchKernel(fn, dim3(nb), dim3(256), args, 0, s);
 }
 
 } // namespace gol

@@ -257,6 +257,7 @@ struct gol_ctx {
     bool halo_exchange = true;   // GOL_OPT_HALO_EXCHANGE (0: diagnostic, the exchange is skipped)
     RuleMasks rule{kLifeBirth, kLifeSurvive};   // gol_set_rule (B3/S23: the tuned kernels)
     bool rule_kernel = false;    // GOL_OPT_RULE_KERNEL: B3/S23 through the rule-generic kernel too
+    bool rule_compiled = true;   // GOL_OPT_RULE_COMPILED: a listed rule runs its compiled kernel
     int64_t text_block_bytes = 64LL << 20;   // snapshot text staging block (GOL_OPT_TEXT_BLOCK_BYTES)
     std::vector<Slab> slabs;     // slabs held by this context
     int cur = 0;                 // parity of the buffer holding the current generation
@@ -402,10 +403,24 @@ int64_t storage_rows(const gol_ctx *c, const Slab &s) { return s.H + 2 * c->hk; 
 // torus, whose single slab is a ring of one.
 bool ring_path(const gol_ctx *c) { return c->nslabs > 1 || c->torus; }
 
-// Life-like rules (gol_set_rule): a launch goes to the rule-generic kernel when
-// the rule is not B3/S23 or GOL_OPT_RULE_KERNEL asks for it.
+// Life-like rules (gol_set_rule): a launch leaves the tuned kernels when the rule
+// is not B3/S23 or GOL_OPT_RULE_KERNEL asks for it (rule_path: for which kernel).
 bool rule_generic(const gol_ctx *c) {
     return c->rule_kernel || c->rule.birth != kLifeBirth || c->rule.survive != kLifeSurvive;
+}
+// What the next launch of this context runs for its rule (GOL_RULE_PATH_*): the
+// tuned kernels, else the rule's compiled kernel where the list (gol_rule.h) and
+// this depth have one, else the rule-generic kernel.  *index: the listed rule.
+int rule_path(const gol_ctx *c, int gens, int *index = nullptr) {
+    if (!rule_generic(c)) return GOL_RULE_PATH_TUNED;
+    if (!c->rule_kernel && c->rule_compiled) {
+        const int i = rule_compiled_index(c->rule.birth, c->rule.survive);
+        if (i >= 0 && bit_crule_supported(gens, c->gw, i)) {
+            if (index) *index = i;
+            return GOL_RULE_PATH_COMPILED;
+        }
+    }
+    return GOL_RULE_PATH_GENERIC;
 }
 // What keeps this context from the rule-generic kernel (nullptr: nothing).
 const char *rule_limit(const gol_ctx *c) {
@@ -664,8 +679,12 @@ int launch_stencil(gol_ctx *c, Slab &s, int gens, int r0, int r1, hipStream_t st
           std::min<int64_t>(s.H + 2 * c->hk, (int64_t)r1 + gens));
     tr_op(c, TR_WRITE, st, nullptr, s.index, c->cur ^ 1, r0, r1);
     if (c->layout == GOL_LAYOUT_BIT) {
-        if (rule_generic(c)) HIPCHK(c, launch_bit_rule(a, gens, c->rule, st));
-        else HIPCHK(c, launch_bit_pipe(a, gens, st));
+        int listed = -1;
+        switch (rule_path(c, gens, &listed)) {
+        case GOL_RULE_PATH_TUNED: HIPCHK(c, launch_bit_pipe(a, gens, st)); break;
+        case GOL_RULE_PATH_COMPILED: HIPCHK(c, launch_bit_crule(a, gens, listed, st)); break;
+        default: HIPCHK(c, launch_bit_rule(a, gens, c->rule, st)); break;
+        }
     } else {
         if (c->byte_core && bytebit_supported(gens))
             HIPCHK(c, launch_bytebit_pipe(a, gens, st, c->byte_core));
@@ -2246,6 +2265,13 @@ int gol_set_option(gol_ctx *c, int option, int64_t value) {
         c->rule_kernel = value != 0;
         return GOL_OK;
     }
+    case GOL_OPT_RULE_COMPILED: {
+        if (value != 0 && value != 1) return fail(c, GOL_EINVAL, "rule compiled must be 0 or 1");
+        if ((value != 0) == c->rule_compiled) return GOL_OK;
+        if (int rc = sync_all(c, nullptr)) return rc;
+        c->rule_compiled = value != 0;
+        return GOL_OK;
+    }
     case GOL_OPT_WORDS_PER_LANE:   // retired in 0.2 (the kernels fix their lane width): accepted, ignored
     case GOL_OPT_SPLIT:            // retired in 0.2 (boundary bands always split off): accepted, ignored
         return GOL_OK;
@@ -2312,6 +2338,21 @@ int gol_get_rule(gol_ctx *c, uint32_t *birth, uint32_t *survive) {
     return GOL_OK;
 }
 
+// The rules with compiled kernels, in list order (host only, no context).
+int gol_compiled_rule(int index, uint32_t *birth, uint32_t *survive, const char **name) {
+    if (index < 0 || index >= kCompiledRuleCount) return GOL_EINVAL;
+    if (birth) *birth = kCompiledRules[index].birth;
+    if (survive) *survive = kCompiledRules[index].survive;
+    if (name) *name = kCompiledRules[index].name;
+    return GOL_OK;
+}
+
+int gol_rule_path(gol_ctx *c, int *path) {
+    if (!c || !path) return GOL_EINVAL;
+    *path = rule_path(c, c->K);
+    return GOL_OK;
+}
+
 int gol_get_option(gol_ctx *c, int option, int64_t *value) {
     if (!c || !value) return GOL_EINVAL;
     switch (option) {
@@ -2326,6 +2367,7 @@ int gol_get_option(gol_ctx *c, int option, int64_t *value) {
     case GOL_OPT_COMM_TIMING: *value = c->comm_timing; return GOL_OK;
     case GOL_OPT_HALO_EXCHANGE: *value = c->halo_exchange; return GOL_OK;
     case GOL_OPT_RULE_KERNEL: *value = c->rule_kernel; return GOL_OK;
+    case GOL_OPT_RULE_COMPILED: *value = c->rule_compiled; return GOL_OK;
     case GOL_OPT_WORDS_PER_LANE: *value = c->layout == GOL_LAYOUT_BIT ? c->gw : 4; return GOL_OK;
     case GOL_OPT_SPLIT: *value = 1; return GOL_OK;
     default: return fail(c, GOL_EINVAL, "unknown option %d", option);

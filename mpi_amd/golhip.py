@@ -35,6 +35,8 @@ OPT_SCHED_TRACE = 13
 OPT_COMM_TIMING = 14
 OPT_HALO_EXCHANGE = 15
 OPT_RULE_KERNEL = 16
+OPT_RULE_COMPILED = 17
+RULE_PATHS = ("tuned", "generic", "compiled")   # GOL_RULE_PATH_*
 # retired in 0.2 (accepted by gol_set_option as no-ops; kept so old callers still run)
 OPT_WORDS_PER_LANE = 3
 OPT_SPLIT = 6
@@ -54,6 +56,7 @@ EXPORTS = [
     "gol_upload_bits", "gol_upload_bits_window",
     "gol_fill_threshold", "gol_fill_random", "gol_fill_random_window",
     "gol_copy_window", "gol_copy",
+    "gol_compiled_rule", "gol_rule_path",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -134,6 +137,8 @@ def load() -> ctypes.CDLL:
         "gol_fill_random_window": ([P, i64, i64, i64, i64, ctypes.c_uint64, ctypes.c_uint64], i32),
         "gol_copy_window": ([P, i64, i64, P, i64, i64, i64, i64, i32], i32),
         "gol_copy": ([P, P], i32),
+        "gol_compiled_rule": ([i32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_char_p)], i32),
+        "gol_rule_path": ([P, ctypes.POINTER(i32)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -164,6 +169,17 @@ def parse_rule(text: str) -> tuple[int, int]:
     if rc:
         raise GolError(rc, f"gol_parse_rule: not a B/S rule: {text!r}")
     return b.value, s.value
+
+
+def compiled_rules() -> list[tuple[str, int, int]]:
+    """(name, birth, survive) of every rule with a kernel compiled for it, in list order
+    (gol_compiled_rule).  Host-only."""
+    out = []
+    while True:
+        b, s, name = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_char_p()
+        if load().gol_compiled_rule(len(out), ctypes.byref(b), ctypes.byref(s), ctypes.byref(name)):
+            return out
+        out.append((name.value.decode(), b.value, s.value))
 
 
 def density_dims(nrows: int, ncols: int, tile_rows: int, tile_cols: int) -> tuple[int, int]:
@@ -322,6 +338,14 @@ class Engine:
         b, s = ctypes.c_uint32(), ctypes.c_uint32()
         self._chk(self.lib.gol_get_rule(self._c, ctypes.byref(b), ctypes.byref(s)), "gol_get_rule")
         return b.value, s.value
+
+    @property
+    def rule_path(self) -> str:
+        """What the next step launches for the rule in force: "tuned" (B3/S23), "compiled"
+        (a rule of compiled_rules(), OPT_RULE_COMPILED) or "generic" (gol_rule_path)."""
+        p = ctypes.c_int()
+        self._chk(self.lib.gol_rule_path(self._c, ctypes.byref(p)), "gol_rule_path")
+        return RULE_PATHS[p.value]
 
     # ------------------------------------------------------------ board state
     def initialize_board(self, mode: str = "stream", seed: int = 1):

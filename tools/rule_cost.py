@@ -3,7 +3,9 @@
 (GOL_OPT_RULE_KERNEL = 1) against B3/S23 on the tuned kernels (the reference
 for this number) on one GPU — same build, same shape, one process, the boards
 taking turns after a settle phase.  A third board runs HighLife (B36/S23), as a
-check that the rule's content does not matter.
+check that the rule's content does not matter.  Further boards run HighLife and
+Day & Night on their compiled kernels (GOL_OPT_RULE_COMPILED = 1, the default)
+beside the same rules on the rule-generic kernel.
 
     python tools/rule_cost.py [--spec N:K ...] [--rounds 4] [--window-s 0.4] [--out FILE]
 
@@ -14,7 +16,8 @@ that idled); then, per round and per board, one timed window
 beside the clock probe (the probe's wave takes registers on one SIMD, so the
 timed window runs without it, as in bench.py).  One JSON line per window, then
 one summary line per spec: median ms per k-step of every board, the ratios to
-the tuned board, the clocks.  A measurement, not a gate.
+the tuned board, of each compiled board to the tuned board and to the generic
+board of its rule, the clocks.  A measurement, not a gate.
 """
 import argparse
 import json
@@ -31,7 +34,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mpi_amd import golhip as gh  # noqa: E402
 
 PROBE_MAX_MS = 20000.0
-BOARDS = {"tuned": ("B3/S23", 0), "generic": ("B3/S23", 1), "highlife": ("B36/S23", 1)}
+# board: (rule, GOL_OPT_RULE_KERNEL); GOL_OPT_RULE_COMPILED stays at its default, 1
+BOARDS = {"tuned": ("B3/S23", 0), "generic": ("B3/S23", 1), "highlife": ("B36/S23", 1),
+          "daynight": ("B3678/S34678", 1), "highlife_compiled": ("B36/S23", 0),
+          "daynight_compiled": ("B3678/S34678", 0)}
+COMPILED = {"highlife_compiled": "highlife", "daynight_compiled": "daynight"}   # and its generic board
 
 
 def main():
@@ -60,6 +67,8 @@ def main():
             e.set_option(gh.OPT_RULE_KERNEL, generic)
             e.initialize_board("stream", 1)
             e.sync()
+            want = "compiled" if b in COMPILED else "generic" if generic else "tuned"
+            assert e.rule_path == want, (b, e.rule_path)
             boards[b] = e
         # calibration block (on the tuned board), then the settle phase shared by the boards
         t = time.perf_counter()
@@ -88,7 +97,8 @@ def main():
                 clk = e.clock_stop()[0]
                 ms[b].append(dev_ms / w)
                 mhz[b].append(clk)
-                emit({"spec": sp, "board": b, "rule": BOARDS[b][0], "rule_kernel": BOARDS[b][1], "round": rnd,
+                emit({"spec": sp, "board": b, "rule": BOARDS[b][0], "rule_kernel": BOARDS[b][1],
+                      "rule_path": e.rule_path, "round": rnd,
                       "k_steps": w, "ms_per_k_step": round(dev_ms / w, 5),
                       "gcups": round(n * n * k * w / dev_ms / 1e6, 1), "sclk_mhz_next_window": round(clk, 1)})
         live = {b: e.popcount() for b, e in boards.items()}
@@ -99,6 +109,8 @@ def main():
               "gcups": {b: round(n * n * k / v / 1e6, 1) for b, v in med.items()},
               "generic_over_tuned": round(med["generic"] / med["tuned"], 4),
               "highlife_over_generic": round(med["highlife"] / med["generic"], 4),
+              "compiled_over_tuned": {b: round(med[b] / med["tuned"], 4) for b in COMPILED},
+              "compiled_over_generic": {b: round(med[b] / med[g], 4) for b, g in COMPILED.items()},
               "spread": {b: [round(min(v), 5), round(max(v), 5)] for b, v in ms.items()},
               "sclk_mhz": {b: round(statistics.median(v), 1) for b, v in mhz.items()},
               "live_cells": live, "generic_live_equals_tuned": live["generic"] == live["tuned"],
