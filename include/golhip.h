@@ -21,7 +21,10 @@
  *    is in gol_last_error(ctx).  No exception crosses the ABI.  (The reference
  *    has no error path beyond MPI_Abort, main.cpp:176-197.)
  *  - Host buffers are caller-owned 0/1 bytes, row-major, leading dimension
- *    `ld` (bytes).  Device memory is owned by the context.
+ *    `ld` (bytes).  Device memory is owned by the context.  On upload any
+ *    nonzero byte is a live cell (cells are bools, main.cpp:73): it is stored,
+ *    downloaded and counted as 1; bytes [ncols, ld) of a row are never read,
+ *    and never written on download.
  *  - Coordinates are GLOBAL (row, col) of the rows×cols grid.
  *  - A context is not thread-safe; one host thread drives it.
  *  - gol_step is asynchronous (enqueues on the context's HIP streams);
