@@ -455,10 +455,11 @@ int gol_digest_async(gol_ctx *ctx, uint64_t digest[2]);
  * map (no collective is involved; the caller adds).
  * GOL_EINVAL (message in gol_last_error): a window outside the grid, tile_rows < 1,
  * tile_cols < 32 or not a multiple of 32, col0 not a multiple of 32,
- * tile_rows*tile_cols > 2^32 - 1 (a count is 32 bits), ld < tcols, null pointers.
- * The multiple-of-32 rule is deliberate in this version: every aligned 32-column
- * word of a row then belongs to exactly one tile.  An empty window (nrows == 0 or
- * ncols == 0) is GOL_OK and writes nothing.
+ * tile_rows*tile_cols > 2^32 - 1 (a count is 32 bits), ld < tcols, null pointers;
+ * a refused call writes nothing to `counts`, and elements [tcols, ld) of a row are
+ * never written.  The multiple-of-32 rule is deliberate in this version: every
+ * aligned 32-column word of a row then belongs to exactly one tile.  An empty window
+ * (nrows == 0 or ncols == 0) is GOL_OK and writes nothing.
  *   gol_density         whole grid; synchronises.
  *   gol_density_window  a window; synchronises.
  *   gol_density_async   whole grid, enqueued behind every gol_step so far (no host
