@@ -27,6 +27,7 @@
 #include <array>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/golhip.h"
@@ -391,6 +392,53 @@ int for_col_runs(const gol_ctx *c, int64_t col0, int64_t ncols, F &&fn) {
     return GOL_OK;
 }
 
+// ----- the window plan: what every window call shares before it touches a stream
+
+// Words per column group as the window kernels take it (0: byte layout).
+int group_width(const gol_ctx *c) { return c->layout == GOL_LAYOUT_BIT ? c->gw : 0; }
+
+int check_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols) {
+    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
+        return fail(c, GOL_EINVAL, "window outside the grid");
+    return GOL_OK;
+}
+
+// The rows [r0, r1) of a window that slab s holds; r0 sits at storage row srow.
+struct Piece {
+    Slab *s;
+    int64_t r0, r1, srow;
+    size_t stage;   // pooled staging of a staged read-back (staged_read)
+};
+Piece clip_to_slab(const gol_ctx *c, Slab &s, int64_t row0, int64_t nrows) {
+    const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
+    return {&s, r0, r1, c->hk + (r0 - s.row0), 0};   // (r1 <= r0: nothing of the window here)
+}
+// ... for every slab of this context that holds rows [row0, row0 + nrows), in slab order.
+std::vector<Piece> window_pieces(gol_ctx *c, int64_t row0, int64_t nrows) {
+    std::vector<Piece> pieces;
+    for (auto &s : c->slabs) {
+        const Piece p = clip_to_slab(c, s, row0, nrows);
+        if (p.r1 > p.r0) pieces.push_back(p);
+    }
+    return pieces;
+}
+int64_t rows_held(gol_ctx *c, int64_t row0, int64_t nrows) {
+    int64_t held = 0;
+    for (const Piece &p : window_pieces(c, row0, nrows)) held += p.r1 - p.r0;
+    return held;
+}
+// A window none of whose rows is held here is another rank's business in a rank context,
+// and an error anywhere else.
+int check_local_rows(gol_ctx *c, bool any) {
+    if (!any && c->transport != GOL_XPORT_RCCL) return fail(c, GOL_EINVAL, "window holds no local rows");
+    return GOL_OK;
+}
+// (row0, nrows) of a whole-board call: the grid, or its slab if this is a rank context.
+std::pair<int64_t, int64_t> own_rows(const gol_ctx *c) {
+    if (c->transport != GOL_XPORT_RCCL) return {0, c->rows};
+    return {c->slabs[0].row0, c->slabs[0].H};
+}
+
 void slab_plan(int64_t rows, int world, int rank, int64_t *row0, int64_t *nrows) {
     const int64_t base = rows / world, rem = rows % world;
     *row0 = rank * base + std::min<int64_t>(rank, rem);
@@ -621,8 +669,7 @@ int wrap_rows(gol_ctx *c, Slab &s, int b, int64_t r0, int64_t r1, hipStream_t st
     if (!c->torus || r1 <= r0) return GOL_OK;
     tr_op(c, TR_READ, st, nullptr, s.index, b, r0, r1);
     tr_op(c, TR_WRITE, st, nullptr, s.index, b, r0, r1);
-    HIPCHK(c, launch_wrap_cols(s.buf[b], c->pitch_bytes, r0, r1, c->cols, c->xoff,
-                               c->layout == GOL_LAYOUT_BIT ? c->gw : 0, st));
+    HIPCHK(c, launch_wrap_cols(s.buf[b], c->pitch_bytes, r0, r1, c->cols, c->xoff, group_width(c), st));
     return GOL_OK;
 }
 
@@ -1289,66 +1336,92 @@ int acquire_staging(gol_ctx *c, int device, size_t bytes, size_t *idx) {
 int64_t bits_row_bytes(int64_t ncols) { return (ncols + 7) / 8; }
 int64_t bits_pitch(int64_t ncols) { return (ncols + 31) / 32 * 4; }
 
-// Enqueue a copy of a window as it stands after every step enqueued so far:
+// The joins before a read-back of storage rows [srow, srow + nr) of slab s's current buffer on
+// its compute stream: the last step's boundary bands run on the comm stream, a split
+// interior's other parts on streams of their own.
+int read_begin(gol_ctx *c, Slab &s, int64_t srow, int64_t nr) {
+    hipEvent_t e;
+    HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const hipError_t e1 = tr_record(c, e, s.comm);
+    const hipError_t e2 = e1 == hipSuccess ? tr_wait(c, s.comp, e) : e1;
+    (void)hipEventDestroy(e);
+    HIPCHK(c, e2);
+    if (int rc = join_parts(c, s, s.comp)) return rc;
+    tr_op(c, TR_READ, s.comp, nullptr, s.index, c->cur, srow, srow + nr);
+    return GOL_OK;
+}
+
+// The fence behind it, once the read-back's last copy is enqueued.
+// The other streams of the slab wait for later steps' events only, recorded after
+// other work than this copy on the compute stream (a split interior's parts wait for
+// seam bands; without overlap the whole step runs on the comm stream): they must
+// wait for the copy before a later step (the step after next) overwrites these rows
+// (found by the schedule check, tests/test_gpu_sched.py)
+int read_end(gol_ctx *c, Slab &s) {
+    if (!s.nx && s.comm == s.comp) return GOL_OK;
+    hipEvent_t f;
+    HIPCHK(c, hipEventCreateWithFlags(&f, hipEventDisableTiming));
+    hipError_t f1 = tr_record(c, f, s.comp);
+    if (f1 == hipSuccess && s.comm != s.comp) f1 = tr_wait(c, s.comm, f);
+    for (int j = 0; j < s.nx && f1 == hipSuccess; ++j) f1 = tr_wait(c, s.part[j], f);
+    (void)hipEventDestroy(f);
+    HIPCHK(c, f1);
+    return GOL_OK;
+}
+
+// The staged read-backs (window_async, density_enqueue).  All staging, bytes(p) per piece, is
+// acquired before anything is enqueued; then, piece by piece on the slab's compute stream,
+// enqueue(p) runs between read_begin and read_end.  The caller registers its buffer with
+// sync_all only after GOL_OK: a failed call leaves no pending write into the caller's memory
+// (its staging stays busy until the next sync, as copies may be in flight).
+template <typename B, typename E>
+int staged_read(gol_ctx *c, std::vector<Piece> &pieces, B &&bytes, E &&enqueue) {
+    for (size_t i = 0; i < pieces.size(); ++i)
+        if (int rc = acquire_staging(c, pieces[i].s->device, bytes(pieces[i]), &pieces[i].stage)) {
+            for (size_t j = 0; j < i; ++j) c->staging[pieces[j].stage].busy = false;   // nothing enqueued yet
+            return rc;
+        }
+    auto one = [&](const Piece &p) -> int {
+        HIPCHK(c, hipSetDevice(p.s->device));
+        if (int rc = read_begin(c, *p.s, p.srow, p.r1 - p.r0)) return rc;
+        if (int rc = enqueue(p)) return rc;
+        return read_end(c, *p.s);
+    };
+    for (const Piece &p : pieces)
+        if (int rc = one(p)) {
+            for (const Piece &q : pieces) c->release_at_sync.push_back(q.stage);
+            return rc;
+        }
+    return GOL_OK;
+}
+
+// Enqueue a copy of a window as it stands after every step enqueued so far (staged_read):
 // unpack (bit) or gather (byte) into device staging on the slab's compute
 // stream, then an async D2H copy into pinned staging; sync_all delivers it.
-// All staging is acquired before anything is enqueued, and the caller's
-// buffer is registered for delivery only once every slab's copy is enqueued:
-// a failed call leaves no pending write into the caller's memory (its staging
-// stays busy until the next sync, as copies may be in flight).
 // packed (gol_download_bits*): the rows leave as bits, MSB first (gol_bits.h).  The
 // device staging holds packed rows of whole dwords (bits_pitch), cleared on the
 // compute stream before one launch_get_bits per column run ORs its cells in;
 // sync_all delivers gol_bits_row_bytes(ncols) bytes of each row.
 int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host, int64_t ld,
                  bool packed = false) {
-    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
-        return fail(c, GOL_EINVAL, "window outside the grid");
+    if (int rc = check_window(c, row0, col0, nrows, ncols)) return rc;
     if (packed && ld < bits_row_bytes(ncols)) return fail(c, GOL_EINVAL, "ld < gol_bits_row_bytes(ncols)");
     if (!packed && ld < ncols) return fail(c, GOL_EINVAL, "ld < ncols");
     if (nrows == 0 || ncols == 0) return GOL_OK;
     const int64_t spitch = packed ? bits_pitch(ncols) : ncols;   // bytes per staging row
-    int64_t held = 0;
-    for (auto &s : c->slabs) held += std::max<int64_t>(0, std::min(row0 + nrows, s.row0 + s.H) - std::max(row0, s.row0));
-    if (held != nrows) return fail(c, GOL_EINVAL, "window rows are not all held by this context");
-    struct Piece {
-        Slab *s;
-        int64_t r0, r1;
-        size_t stage;
-    };
-    std::vector<Piece> pieces;
-    for (auto &s : c->slabs) {
-        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
-        if (r1 <= r0) continue;
-        size_t st = 0;
-        if (int rc = acquire_staging(c, s.device, (size_t)((r1 - r0) * spitch), &st)) {
-            for (auto &p : pieces) c->staging[p.stage].busy = false;   // nothing enqueued yet
-            return rc;
-        }
-        pieces.push_back({&s, r0, r1, st});
-    }
+    if (rows_held(c, row0, nrows) != nrows) return fail(c, GOL_EINVAL, "window rows are not all held by this context");
+    std::vector<Piece> pieces = window_pieces(c, row0, nrows);
+    auto bytes = [&](const Piece &p) { return (size_t)((p.r1 - p.r0) * spitch); };
     auto enqueue = [&](const Piece &p) -> int {
         Slab &s = *p.s;
         Staging &buf = c->staging[p.stage];
-        const int64_t nr = p.r1 - p.r0;
-        HIPCHK(c, hipSetDevice(s.device));
-        // the last step's boundary bands run on the comm stream: join it
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        const hipError_t e1 = tr_record(c, e, s.comm);
-        const hipError_t e2 = e1 == hipSuccess ? tr_wait(c, s.comp, e) : e1;
-        (void)hipEventDestroy(e);
-        HIPCHK(c, e2);
-        if (int rc = join_parts(c, s, s.comp)) return rc;   // (a split interior's other parts)
-        const int64_t srow = c->hk + (p.r0 - s.row0);
-        tr_op(c, TR_READ, s.comp, nullptr, s.index, c->cur, srow, srow + nr);
-        if (packed) HIPCHK(c, hipMemsetAsync(buf.dtmp, 0, (size_t)(nr * spitch), s.comp));
+        const int64_t srow = p.srow, nr = p.r1 - p.r0;
+        if (packed) HIPCHK(c, hipMemsetAsync(buf.dtmp, 0, bytes(p), s.comp));
         int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
             uint8_t *d = buf.dtmp + (lc - col0);
             if (packed)
                 HIPCHK(c, launch_get_bits(s.buf[c->cur], c->pitch_bytes, srow, srow + nr, pc, lc - col0, n,
-                                          reinterpret_cast<uint32_t *>(buf.dtmp), spitch / 4,
-                                          c->layout == GOL_LAYOUT_BIT ? c->gw : 0, s.comp));
+                                          reinterpret_cast<uint32_t *>(buf.dtmp), spitch / 4, group_width(c), s.comp));
             else if (c->layout == GOL_LAYOUT_BYTE)
                 HIPCHK(c, hipMemcpy2DAsync(d, ncols, static_cast<uint8_t *>(s.buf[c->cur]) + srow * c->pitch_bytes + pc,
                                            c->pitch_bytes, n, nr, hipMemcpyDeviceToDevice, s.comp));
@@ -1358,29 +1431,10 @@ int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t 
             return GOL_OK;
         });
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(buf.pinned, buf.dtmp, (size_t)(nr * spitch), hipMemcpyDeviceToHost, s.comp));
-        // The other streams of the slab wait for later steps' events only, recorded after
-        // other work than this copy on the compute stream (a split interior's parts wait for
-        // seam bands; without overlap the whole step runs on the comm stream): they must
-        // wait for the copy before a later step overwrites these rows (found by the
-        // schedule check, tests/test_gpu_sched.py)
-        if (s.nx || s.comm != s.comp) {
-            hipEvent_t f;
-            HIPCHK(c, hipEventCreateWithFlags(&f, hipEventDisableTiming));
-            hipError_t f1 = tr_record(c, f, s.comp);
-            if (f1 == hipSuccess && s.comm != s.comp) f1 = tr_wait(c, s.comm, f);
-            for (int j = 0; j < s.nx && f1 == hipSuccess; ++j) f1 = tr_wait(c, s.part[j], f);
-            (void)hipEventDestroy(f);
-            HIPCHK(c, f1);
-        }
+        HIPCHK(c, hipMemcpyAsync(buf.pinned, buf.dtmp, bytes(p), hipMemcpyDeviceToHost, s.comp));
         return GOL_OK;
     };
-    for (const auto &p : pieces) {
-        if (int rc = enqueue(p)) {
-            for (auto &q : pieces) c->release_at_sync.push_back(q.stage);
-            return rc;
-        }
-    }
+    if (int rc = staged_read(c, pieces, bytes, enqueue)) return rc;
     for (const auto &p : pieces) {
         PendingWindow w;
         w.stage = p.stage;
@@ -1397,16 +1451,15 @@ int window_async(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t 
 // ----------------------------------------------------------------------- digest
 
 // Enqueue the digest (gol_digest.h) of the window as it stands after every step
-// enqueued so far: per slab, on its compute stream behind the joins window_async
-// makes, the slab's slot is cleared, one launch per storage-contiguous column run
+// enqueued so far: per slab, on its compute stream between read_begin and read_end,
+// the slab's slot is cleared, one launch per storage-contiguous column run
 // adds the cells of the window this slab holds (exact ranges: no pad column,
 // ghost column or halo row is read as a cell), and the slot goes to its pinned
 // mirror; sync_all sums the slabs into `out`.  Rows this context does not hold
 // contribute nothing.  `out` is registered only once every slab is enqueued: a
 // failed call leaves no pending write (its slot is cleared again by the next call).
 int digest_enqueue(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint64_t *out) {
-    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
-        return fail(c, GOL_EINVAL, "window outside the grid");
+    if (int rc = check_window(c, row0, col0, nrows, ncols)) return rc;
     const size_t slot = c->pending_digests.size();
     if (slot >= kDigestRing)
         return fail(c, GOL_ESTATE, "%zu digests are pending: sync first", kDigestRing);
@@ -1425,44 +1478,25 @@ int digest_enqueue(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_
             return fail(c, GOL_ENOMEM, "pinned digest slots");
         }
     }
-    const int gw = c->layout == GOL_LAYOUT_BIT ? c->gw : 0;
     for (auto &s : c->slabs) {
         HIPCHK(c, hipSetDevice(s.device));
         unsigned long long *d = s.dg_dev + 2 * slot;
-        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
-        if (r1 <= r0 || ncols == 0) {   // nothing of the window here: the slab's part is (0, 0)
+        const Piece p = clip_to_slab(c, s, row0, nrows);
+        if (p.r1 <= p.r0 || ncols == 0) {   // nothing of the window here: the slab's part is (0, 0)
             HIPCHK(c, hipMemsetAsync(d, 0, 2 * sizeof *d, s.comp));
             HIPCHK(c, hipMemcpyAsync(s.dg_host + 2 * slot, d, 2 * sizeof *d, hipMemcpyDeviceToHost, s.comp));
             continue;
         }
-        // the last step's boundary bands run on the comm stream: join it
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        const hipError_t e1 = tr_record(c, e, s.comm);
-        const hipError_t e2 = e1 == hipSuccess ? tr_wait(c, s.comp, e) : e1;
-        (void)hipEventDestroy(e);
-        HIPCHK(c, e2);
-        if (int rc = join_parts(c, s, s.comp)) return rc;   // (a split interior's other parts)
-        const int64_t srow = c->hk + (r0 - s.row0);
-        tr_op(c, TR_READ, s.comp, nullptr, s.index, c->cur, srow, srow + (r1 - r0));
+        if (int rc = read_begin(c, s, p.srow, p.r1 - p.r0)) return rc;
         HIPCHK(c, hipMemsetAsync(d, 0, 2 * sizeof *d, s.comp));
         int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
-            HIPCHK(c, launch_digest(s.buf[c->cur], c->pitch_bytes, srow, srow + (r1 - r0), r0, pc, lc, n, d, gw, s.comp));
+            HIPCHK(c, launch_digest(s.buf[c->cur], c->pitch_bytes, p.srow, p.srow + (p.r1 - p.r0), p.r0, pc, lc, n, d,
+                                    group_width(c), s.comp));
             return GOL_OK;
         });
         if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync(s.dg_host + 2 * slot, d, 2 * sizeof *d, hipMemcpyDeviceToHost, s.comp));
-        // as window_async: the slab's other streams wait for the read before a later
-        // step (the step after next) overwrites this buffer
-        if (s.nx || s.comm != s.comp) {
-            hipEvent_t f;
-            HIPCHK(c, hipEventCreateWithFlags(&f, hipEventDisableTiming));
-            hipError_t f1 = tr_record(c, f, s.comp);
-            if (f1 == hipSuccess && s.comm != s.comp) f1 = tr_wait(c, s.comm, f);
-            for (int j = 0; j < s.nx && f1 == hipSuccess; ++j) f1 = tr_wait(c, s.part[j], f);
-            (void)hipEventDestroy(f);
-            HIPCHK(c, f1);
-        }
+        if (int rc2 = read_end(c, s)) return rc2;
     }
     PendingDigest p;
     p.out = out;
@@ -1493,18 +1527,14 @@ void density_dims(int64_t nrows, int64_t ncols, int64_t tile_rows, int64_t tile_
 }
 
 // Enqueue the density map (gol_density.h) of the window as it stands after every
-// step enqueued so far.  Per slab that holds rows of the window, on its compute
-// stream behind the joins digest_enqueue makes: the slab's part (pooled staging:
-// the tile rows its rows touch) is cleared, one launch per storage-contiguous
-// column run adds the cells of the window this slab holds (exact ranges, as the
-// digest's), and the part goes to its pinned mirror; sync_all adds the parts into
-// `counts`.  All staging is acquired before anything is enqueued and `counts` is
-// registered only once every slab is enqueued: a failed call leaves no pending
-// write (its staging stays busy until the next sync, as work may be in flight).
+// step enqueued so far (staged_read).  Per slab that holds rows of the window: the
+// slab's part (pooled staging: the tile rows its rows touch) is cleared, one launch
+// per storage-contiguous column run adds the cells of the window this slab holds
+// (exact ranges, as the digest's), and the part goes to its pinned mirror; sync_all
+// adds the parts into `counts`.
 int density_enqueue(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int64_t tile_rows,
                     int64_t tile_cols, uint32_t *counts, int64_t ld) {
-    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
-        return fail(c, GOL_EINVAL, "window outside the grid");
+    if (int rc = check_window(c, row0, col0, nrows, ncols)) return rc;
     if (tile_rows < 1) return fail(c, GOL_EINVAL, "tile_rows < 1");
     if (tile_cols < 32 || tile_cols % 32) return fail(c, GOL_EINVAL, "tile_cols must be a multiple of 32 (>= 32)");
     if (col0 % 32) return fail(c, GOL_EINVAL, "col0 must be a multiple of 32");
@@ -1514,74 +1544,38 @@ int density_enqueue(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64
     density_dims(nrows, ncols, tile_rows, tile_cols, &trows, &tcols);
     if (ld < tcols) return fail(c, GOL_EINVAL, "ld < tcols");
     if (nrows == 0 || ncols == 0) return GOL_OK;
-    struct Piece {
-        Slab *s;
-        int64_t r0, r1;
-        PendingDensity::Part part;
+    // (a slab that holds nothing of the window adds nothing)
+    std::vector<Piece> pieces = window_pieces(c, row0, nrows);
+    auto part = [&](const Piece &p) {   // the tile rows the piece's rows touch
+        PendingDensity::Part q;
+        q.stage = p.stage;
+        q.ti0 = (p.r0 - row0) / tile_rows;
+        q.ntr = (p.r1 - 1 - row0) / tile_rows - q.ti0 + 1;
+        return q;
     };
-    std::vector<Piece> pieces;
-    for (auto &s : c->slabs) {
-        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
-        if (r1 <= r0) continue;   // nothing of the window here: this slab adds nothing
-        Piece p{&s, r0, r1, {}};
-        p.part.ti0 = (r0 - row0) / tile_rows;
-        p.part.ntr = (r1 - 1 - row0) / tile_rows - p.part.ti0 + 1;
-        if (int rc = acquire_staging(c, s.device, (size_t)(p.part.ntr * tcols) * sizeof(uint32_t), &p.part.stage)) {
-            for (auto &q : pieces) c->staging[q.part.stage].busy = false;   // nothing enqueued yet
-            return rc;
-        }
-        pieces.push_back(p);
-    }
-    const int gw = c->layout == GOL_LAYOUT_BIT ? c->gw : 0;
+    auto bytes = [&](const Piece &p) { return (size_t)(part(p).ntr * tcols) * sizeof(uint32_t); };
     auto enqueue = [&](const Piece &p) -> int {
         Slab &s = *p.s;
-        Staging &buf = c->staging[p.part.stage];
+        Staging &buf = c->staging[p.stage];
         uint32_t *d = reinterpret_cast<uint32_t *>(buf.dtmp);
-        const size_t bytes = (size_t)(p.part.ntr * tcols) * sizeof(uint32_t);
-        HIPCHK(c, hipSetDevice(s.device));
-        // the last step's boundary bands run on the comm stream: join it
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        const hipError_t e1 = tr_record(c, e, s.comm);
-        const hipError_t e2 = e1 == hipSuccess ? tr_wait(c, s.comp, e) : e1;
-        (void)hipEventDestroy(e);
-        HIPCHK(c, e2);
-        if (int rc = join_parts(c, s, s.comp)) return rc;   // (a split interior's other parts)
-        const int64_t srow = c->hk + (p.r0 - s.row0);
-        tr_op(c, TR_READ, s.comp, nullptr, s.index, c->cur, srow, srow + (p.r1 - p.r0));
-        HIPCHK(c, hipMemsetAsync(d, 0, bytes, s.comp));
+        HIPCHK(c, hipMemsetAsync(d, 0, bytes(p), s.comp));
         int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
-            HIPCHK(c, launch_density(s.buf[c->cur], c->pitch_bytes, srow, srow + (p.r1 - p.r0), p.r0 - row0, pc, lc, n,
-                                     col0, tile_rows, tile_cols, d, p.part.ti0, p.part.ntr, tcols, gw, s.comp));
+            HIPCHK(c, launch_density(s.buf[c->cur], c->pitch_bytes, p.srow, p.srow + (p.r1 - p.r0), p.r0 - row0, pc, lc, n,
+                                     col0, tile_rows, tile_cols, d, part(p).ti0, part(p).ntr, tcols, group_width(c),
+                                     s.comp));
             return GOL_OK;
         });
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(buf.pinned, d, bytes, hipMemcpyDeviceToHost, s.comp));
-        // as window_async: the slab's other streams wait for the read before a later
-        // step (the step after next) overwrites this buffer
-        if (s.nx || s.comm != s.comp) {
-            hipEvent_t f;
-            HIPCHK(c, hipEventCreateWithFlags(&f, hipEventDisableTiming));
-            hipError_t f1 = tr_record(c, f, s.comp);
-            if (f1 == hipSuccess && s.comm != s.comp) f1 = tr_wait(c, s.comm, f);
-            for (int j = 0; j < s.nx && f1 == hipSuccess; ++j) f1 = tr_wait(c, s.part[j], f);
-            (void)hipEventDestroy(f);
-            HIPCHK(c, f1);
-        }
+        HIPCHK(c, hipMemcpyAsync(buf.pinned, d, bytes(p), hipMemcpyDeviceToHost, s.comp));
         return GOL_OK;
     };
-    for (const auto &p : pieces) {
-        if (int rc = enqueue(p)) {
-            for (auto &q : pieces) c->release_at_sync.push_back(q.part.stage);
-            return rc;
-        }
-    }
+    if (int rc = staged_read(c, pieces, bytes, enqueue)) return rc;
     PendingDensity m;
     m.out = counts;
     m.ld = ld;
     m.trows = trows;
     m.tcols = tcols;
-    for (const auto &p : pieces) m.parts.push_back(p.part);
+    for (const auto &p : pieces) m.parts.push_back(part(p));
     c->pending_density.push_back(m);
     return GOL_OK;
 }
@@ -1743,6 +1737,15 @@ int enforce_inactive(gol_ctx *c, Slab &s, int buf) {
     return GOL_OK;
 }
 
+// The tail of a device-side write (fill, copy) of storage rows [srow0, srow1) of slab s's
+// current buffer on its compute stream: ghost margins, the inactive region, then the host waits.
+int finish_write(gol_ctx *c, Slab &s, int64_t srow0, int64_t srow1) {
+    if (int rc = wrap_rows(c, s, c->cur, srow0, srow1, s.comp)) return rc;
+    if (int rc = enforce_inactive(c, s, c->cur)) return rc;
+    HIPCHK(c, tr_ssync(c, s.comp));
+    return GOL_OK;
+}
+
 // ------------------------------------------------------------------ windows
 // Host <-> device windows go through the pooled staging (acquire_staging) in
 // row blocks of at most kIoBlock bytes, with stream syncs only: no hipMalloc /
@@ -1776,8 +1779,7 @@ int upload_piece(gol_ctx *c, Slab &s, int64_t r0, int64_t r1, int64_t col0, int6
             const uint8_t *cells = b.dtmp + (lc - col0);
             if (packed) {
                 HIPCHK(c, launch_put_bits(board, c->pitch_bytes, srow, srow + nr, pc, lc - col0, n, c->active_cols,
-                                          reinterpret_cast<const uint32_t *>(b.dtmp), spitch / 4,
-                                          c->layout == GOL_LAYOUT_BIT ? c->gw : 0, s.comp));
+                                          reinterpret_cast<const uint32_t *>(b.dtmp), spitch / 4, group_width(c), s.comp));
             } else if (c->layout == GOL_LAYOUT_BYTE) {
                 uint8_t *d = board + srow * c->pitch_bytes + pc;
                 HIPCHK(c, hipMemcpy2DAsync(d, c->pitch_bytes, cells, ncols, n, nr, hipMemcpyDeviceToDevice, s.comp));
@@ -1803,23 +1805,19 @@ int upload_piece(gol_ctx *c, Slab &s, int64_t r0, int64_t r1, int64_t col0, int6
 
 int window_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host, int64_t ld,
               bool upload, bool packed = false) {
-    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
-        return fail(c, GOL_EINVAL, "window outside the grid");
+    if (int rc = check_window(c, row0, col0, nrows, ncols)) return rc;
     if (packed && ld < bits_row_bytes(ncols)) return fail(c, GOL_EINVAL, "ld < gol_bits_row_bytes(ncols)");
     if (!packed && ld < ncols) return fail(c, GOL_EINVAL, "ld < ncols");
     if (nrows == 0 || ncols == 0) return GOL_OK;
     if (packed && !host) return fail(c, GOL_EINVAL, "null buffer");
     if (int rc = sync_all(c, nullptr)) return rc;
     const int64_t br = std::max<int64_t>(1, kIoBlock / (packed ? bits_pitch(ncols) : ncols));
-    bool any = false;
     // slab by slab (a rank context moves the rows it holds; the others stay untouched)
-    for (size_t si = 0; si < c->slabs.size(); ++si) {
-        Slab &s = c->slabs[si];
-        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
-        if (r1 <= r0) continue;
-        any = true;
-        for (int64_t a = r0; a < r1; a += br) {
-            const int64_t e = std::min(r1, a + br);
+    const std::vector<Piece> pieces = window_pieces(c, row0, nrows);
+    for (const Piece &p : pieces) {
+        Slab &s = *p.s;
+        for (int64_t a = p.r0; a < p.r1; a += br) {
+            const int64_t e = std::min(p.r1, a + br);
             uint8_t *h = host + (a - row0) * ld;
             int rc = upload ? upload_piece(c, s, a, e, col0, ncols, h, ld, packed)
                             : window_async(c, a, col0, e - a, ncols, h, ld, packed);
@@ -1832,8 +1830,7 @@ int window_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t nco
             HIPCHK(c, tr_ssync(c, s.comp));
         }
     }
-    if (!any && c->transport != GOL_XPORT_RCCL) return fail(c, GOL_EINVAL, "window holds no local rows");
-    return GOL_OK;
+    return check_local_rows(c, !pieces.empty());
 }
 
 // ------------------------------------------------------------------ snapshot text
@@ -1899,13 +1896,10 @@ struct TextBuffers {
 };
 
 int text_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, TextHost &h, bool upload) {
-    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
-        return fail(c, GOL_EINVAL, "window outside the grid");
+    if (int rc = check_window(c, row0, col0, nrows, ncols)) return rc;
     if (nrows == 0 || ncols == 0) return GOL_OK;
     // every row of the window must be held here (a rank formats / parses its own part)
-    int64_t held = 0;
-    for (auto &s : c->slabs) held += std::max<int64_t>(0, std::min(row0 + nrows, s.row0 + s.H) - std::max(row0, s.row0));
-    if (held != nrows) return fail(c, GOL_EINVAL, "text window rows are not all held by this context");
+    if (rows_held(c, row0, nrows) != nrows) return fail(c, GOL_EINVAL, "text window rows are not all held by this context");
     // the text path allocates its pinned blocks per call, and an allocation can
     // wait for the whole device (i.e. for a running probe)
     if (c->clk_running) return fail(c, GOL_ESTATE, "snapshot text while the clock probe runs");
@@ -1916,9 +1910,9 @@ int text_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols
     const int64_t rowlen = 2 * ncols + 1;
     const int64_t br = std::max<int64_t>(1, c->text_block_bytes / rowlen);
     const bool bit = c->layout == GOL_LAYOUT_BIT;
-    for (auto &s : c->slabs) {
-        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
-        if (r1 <= r0) continue;
+    for (const Piece &p : window_pieces(c, row0, nrows)) {
+        Slab &s = *p.s;
+        const int64_t r0 = p.r0, r1 = p.r1;
         HIPCHK(c, hipSetDevice(s.device));
         const int64_t nb = (r1 - r0 + br - 1) / br, bmax = std::min(br, r1 - r0);
         TextBuffers t;
@@ -1938,10 +1932,10 @@ int text_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols
         // device part of block i, on the (idle) comm stream, ending with event ev[i&1]
         auto enqueue = [&](int64_t i) -> int {
             const int64_t a = r0 + i * br, nr = rows_of(i), bytes = nr * rowlen;
-            const int64_t srow = c->hk + (a - s.row0);
+            const int64_t srow = p.srow + i * br;
             char *pin = t.pinned[i & 1];
             if (!upload) {
-                HIPCHK(c, launch_format_text(cur, c->pitch_bytes, bit ? c->gw : 0, srow, col0 + c->xoff, nr, ncols,
+                HIPCHK(c, launch_format_text(cur, c->pitch_bytes, group_width(c), srow, col0 + c->xoff, nr, ncols,
                                              c->perm_m, c->perm_L, t.dtext, s.comm));
                 HIPCHK(c, hipMemcpyAsync(pin, t.dtext, (size_t)bytes, hipMemcpyDeviceToHost, s.comm));
             } else {
@@ -2406,11 +2400,8 @@ int gol_init_glibc(gol_ctx *c, int mode, uint32_t seed) {
 
 int gol_upload(gol_ctx *c, const uint8_t *host, int64_t ld) {
     if (!c || !host) return GOL_EINVAL;
-    if (c->transport == GOL_XPORT_RCCL) {
-        const Slab &s = c->slabs[0];
-        return window_io(c, s.row0, 0, s.H, c->cols, const_cast<uint8_t *>(host) + s.row0 * ld, ld, true);
-    }
-    return window_io(c, 0, 0, c->rows, c->cols, const_cast<uint8_t *>(host), ld, true);
+    const auto [row0, nrows] = own_rows(c);
+    return window_io(c, row0, 0, nrows, c->cols, const_cast<uint8_t *>(host) + row0 * ld, ld, true);
 }
 
 int gol_upload_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, const uint8_t *host,
@@ -2421,11 +2412,8 @@ int gol_upload_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int
 
 int gol_download(gol_ctx *c, uint8_t *host, int64_t ld) {
     if (!c || !host) return GOL_EINVAL;
-    if (c->transport == GOL_XPORT_RCCL) {
-        const Slab &s = c->slabs[0];
-        return window_io(c, s.row0, 0, s.H, c->cols, host + s.row0 * ld, ld, false);
-    }
-    return window_io(c, 0, 0, c->rows, c->cols, host, ld, false);
+    const auto [row0, nrows] = own_rows(c);
+    return window_io(c, row0, 0, nrows, c->cols, host + row0 * ld, ld, false);
 }
 
 int gol_download_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host,
@@ -2442,11 +2430,8 @@ int64_t gol_bits_row_bytes(int64_t ncols) {
 // (a null buffer is refused with a message unless the window is empty: window_io, bits_window_async)
 int gol_download_bits(gol_ctx *c, uint8_t *host, int64_t ld) {
     if (!c) return GOL_EINVAL;
-    if (c->transport == GOL_XPORT_RCCL && host) {
-        const Slab &s = c->slabs[0];
-        return window_io(c, s.row0, 0, s.H, c->cols, host + s.row0 * ld, ld, false, true);
-    }
-    return window_io(c, 0, 0, c->rows, c->cols, host, ld, false, true);
+    const auto [row0, nrows] = own_rows(c);
+    return window_io(c, row0, 0, nrows, c->cols, host ? host + row0 * ld : host, ld, false, true);
 }
 
 int gol_download_bits_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint8_t *host,
@@ -2464,11 +2449,9 @@ int gol_download_bits_window_async(gol_ctx *c, int64_t row0, int64_t col0, int64
 
 int gol_upload_bits(gol_ctx *c, const uint8_t *host, int64_t ld) {
     if (!c) return GOL_EINVAL;
-    if (c->transport == GOL_XPORT_RCCL && host) {
-        const Slab &s = c->slabs[0];
-        return window_io(c, s.row0, 0, s.H, c->cols, const_cast<uint8_t *>(host) + s.row0 * ld, ld, true, true);
-    }
-    return window_io(c, 0, 0, c->rows, c->cols, const_cast<uint8_t *>(host), ld, true, true);
+    const auto [row0, nrows] = own_rows(c);
+    uint8_t *rows = const_cast<uint8_t *>(host);
+    return window_io(c, row0, 0, nrows, c->cols, rows ? rows + row0 * ld : rows, ld, true, true);
 }
 
 int gol_upload_bits_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, const uint8_t *host,
@@ -2491,41 +2474,32 @@ int gol_fill_threshold(double density, uint64_t *threshold) {
 int gol_fill_random_window(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, uint64_t seed,
                            uint64_t threshold) {
     if (!c) return GOL_EINVAL;
-    if (nrows < 0 || ncols < 0 || row0 < 0 || col0 < 0 || row0 + nrows > c->rows || col0 + ncols > c->cols)
-        return fail(c, GOL_EINVAL, "window outside the grid");
+    if (int rc = check_window(c, row0, col0, nrows, ncols)) return rc;
     if (threshold > kFillFull) return fail(c, GOL_EINVAL, "threshold above 2^32 (the density is threshold / 2^32)");
     if (nrows == 0 || ncols == 0) return GOL_OK;
     if (int rc = sync_all(c, nullptr)) return rc;
     const uint64_t K = fill_key(seed);
-    bool any = false;
-    for (auto &s : c->slabs) {
-        const int64_t r0 = std::max(row0, s.row0), r1 = std::min(row0 + nrows, s.row0 + s.H);
-        if (r1 <= r0) continue;
-        any = true;
-        const int64_t srow = c->hk + (r0 - s.row0), nr = r1 - r0;
+    const std::vector<Piece> pieces = window_pieces(c, row0, nrows);
+    for (const Piece &p : pieces) {
+        Slab &s = *p.s;
+        const int64_t srow1 = p.srow + (p.r1 - p.r0);
         HIPCHK(c, hipSetDevice(s.device));
-        tr_op(c, TR_WRITE, s.comp, nullptr, s.index, c->cur, srow, srow + nr);
+        tr_op(c, TR_WRITE, s.comp, nullptr, s.index, c->cur, p.srow, srow1);
         int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
-            HIPCHK(c, launch_fill_random(s.buf[c->cur], c->pitch_bytes, srow, srow + nr, r0, pc, lc, n, c->active_cols,
-                                         K, threshold, c->layout == GOL_LAYOUT_BIT ? c->gw : 0, s.comp));
+            HIPCHK(c, launch_fill_random(s.buf[c->cur], c->pitch_bytes, p.srow, srow1, p.r0, pc, lc, n, c->active_cols,
+                                         K, threshold, group_width(c), s.comp));
             return GOL_OK;
         });
-        if (!rc) rc = wrap_rows(c, s, c->cur, srow, srow + nr, s.comp);
-        if (!rc) rc = enforce_inactive(c, s, c->cur);
+        if (!rc) rc = finish_write(c, s, p.srow, srow1);
         if (rc) return rc;
-        HIPCHK(c, tr_ssync(c, s.comp));
     }
-    if (!any && c->transport != GOL_XPORT_RCCL) return fail(c, GOL_EINVAL, "window holds no local rows");
-    return GOL_OK;
+    return check_local_rows(c, !pieces.empty());
 }
 
 int gol_fill_random(gol_ctx *c, uint64_t seed, uint64_t threshold) {
     if (!c) return GOL_EINVAL;
-    if (c->transport == GOL_XPORT_RCCL) {
-        const Slab &s = c->slabs[0];
-        return gol_fill_random_window(c, s.row0, 0, s.H, c->cols, seed, threshold);
-    }
-    return gol_fill_random_window(c, 0, 0, c->rows, c->cols, seed, threshold);
+    const auto [row0, nrows] = own_rows(c);
+    return gol_fill_random_window(c, row0, 0, nrows, c->cols, seed, threshold);
 }
 
 // ------------------------------------------------------------------ board-to-board copy
@@ -2548,72 +2522,49 @@ int gol_copy_window(gol_ctx *d, int64_t drow0, int64_t dcol0, gol_ctx *c, int64_
     if (nrows == 0 || ncols == 0) return GOL_OK;
     if (c == d && drow0 < srow0 + nrows && srow0 < drow0 + nrows && dcol0 < scol0 + ncols && scol0 < dcol0 + ncols)
         return fail(d, GOL_EINVAL, "source and destination rectangles of one context overlap");
-    // the row pieces: rows [r0, r1) of the destination window held by destination slab di,
-    // whose source rows r + (srow0 - drow0) are held by source slab si
-    struct Piece {
-        size_t di, si;
-        int64_t r0, r1;
-    };
-    std::vector<Piece> pieces;
+    // the row pieces: the rows dp of the destination window held by a destination slab, and
+    // the pieces sp of their source rows r + shift held by the source slabs
     const int64_t shift = srow0 - drow0;
-    bool any = false;
-    for (size_t di = 0; di < d->slabs.size(); ++di) {
-        const Slab &ds = d->slabs[di];
-        const int64_t a = std::max(drow0, ds.row0), b = std::min(drow0 + nrows, ds.row0 + ds.H);
-        if (b <= a) continue;
-        any = true;
+    const std::vector<Piece> dpieces = window_pieces(d, drow0, nrows);
+    for (const Piece &dp : dpieces) {
         int64_t held = 0;
-        for (size_t si = 0; si < c->slabs.size(); ++si) {
-            const Slab &ss = c->slabs[si];
-            const int64_t r0 = std::max(a, ss.row0 - shift), r1 = std::min(b, ss.row0 + ss.H - shift);
-            if (r1 <= r0) continue;
-            held += r1 - r0;
-            if (ss.device != ds.device)
+        for (const Piece &sp : window_pieces(c, dp.r0 + shift, dp.r1 - dp.r0)) {   // (in SOURCE rows)
+            held += sp.r1 - sp.r0;
+            if (sp.s->device != dp.s->device)
                 return fail(d, GOL_EUNSUPPORTED,
                             "source rows [%lld, %lld) live on device %d, their destination rows on device %d: this "
                             "version copies within a device",
-                            (long long)(r0 + shift), (long long)(r1 + shift), ss.device, ds.device);
-            pieces.push_back({di, si, r0, r1});
+                            (long long)sp.r0, (long long)sp.r1, sp.s->device, dp.s->device);
         }
-        if (held != b - a)
+        if (held != dp.r1 - dp.r0)
             return fail(d, GOL_EINVAL, "the source context does not hold every source row of destination rows [%lld, %lld)",
-                        (long long)a, (long long)b);
+                        (long long)dp.r0, (long long)dp.r1);
     }
-    if (!any && d->transport != GOL_XPORT_RCCL) return fail(d, GOL_EINVAL, "window holds no local rows");
+    if (int rc = check_local_rows(d, !dpieces.empty())) return rc;
     if (int rc = sync_all(c, nullptr)) return c == d ? rc : fail(d, rc, "synchronising the source: %s", c->err.c_str());
     if (c != d)
         if (int rc = sync_all(d, nullptr)) return rc;
-    const int sgw = c->layout == GOL_LAYOUT_BIT ? c->gw : 0, dgw = d->layout == GOL_LAYOUT_BIT ? d->gw : 0;
-    for (size_t di = 0; di < d->slabs.size(); ++di) {
-        Slab &ds = d->slabs[di];
-        int64_t lo = -1, hi = -1;   // destination rows of this slab's pieces
+    for (const Piece &dp : dpieces) {
+        Slab &ds = *dp.s;
         HIPCHK(d, hipSetDevice(ds.device));
-        for (const Piece &p : pieces) {
-            if (p.di != di) continue;
-            const Slab &ss = c->slabs[p.si];
-            const int64_t nr = p.r1 - p.r0;
-            const int64_t drow = d->hk + (p.r0 - ds.row0), srow = c->hk + (p.r0 + shift - ss.row0);
-            lo = lo < 0 ? p.r0 : std::min(lo, p.r0);
-            hi = std::max(hi, p.r1);
+        for (const Piece &sp : window_pieces(c, dp.r0 + shift, dp.r1 - dp.r0)) {
+            const Slab &ss = *sp.s;
+            const int64_t nr = sp.r1 - sp.r0;
+            const int64_t drow = dp.srow + (sp.r0 - shift - dp.r0), srow = sp.srow;
             tr_op(c, TR_READ, ds.comp, nullptr, ss.index, c->cur, srow, srow + nr);
             tr_op(d, TR_WRITE, ds.comp, nullptr, ds.index, d->cur, drow, drow + nr);
             int rc = for_col_runs(d, dcol0, ncols, [&](int64_t dlc, int64_t dpc, int64_t dn) -> int {
                 return for_col_runs(c, scol0 + (dlc - dcol0), dn, [&](int64_t slc, int64_t spc, int64_t n) -> int {
                     const int64_t off = slc - (scol0 + (dlc - dcol0));   // of this source run inside the destination run
-                    HIPCHK(d, launch_copy_cells(ss.buf[c->cur], c->pitch_bytes, srow, spc, sgw, ds.buf[d->cur],
-                                                d->pitch_bytes, drow, dpc + off, dgw, nr, n, d->active_cols, op,
-                                                ds.comp));
+                    HIPCHK(d, launch_copy_cells(ss.buf[c->cur], c->pitch_bytes, srow, spc, group_width(c), ds.buf[d->cur],
+                                                d->pitch_bytes, drow, dpc + off, group_width(d), nr, n, d->active_cols,
+                                                op, ds.comp));
                     return GOL_OK;
                 });
             });
             if (rc) return rc;
         }
-        if (lo < 0) continue;
-        const int64_t w0 = d->hk + (lo - ds.row0), w1 = d->hk + (hi - ds.row0);
-        int rc = wrap_rows(d, ds, d->cur, w0, w1, ds.comp);
-        if (!rc) rc = enforce_inactive(d, ds, d->cur);
-        if (rc) return rc;
-        HIPCHK(d, tr_ssync(d, ds.comp));
+        if (int rc = finish_write(d, ds, dp.srow, dp.srow + (dp.r1 - dp.r0))) return rc;
         if (c != d) tr_op(c, TR_STREAM_SYNC, ds.comp, nullptr);   // the source's trace: its reads are complete
     }
     return GOL_OK;
@@ -2624,11 +2575,8 @@ int gol_copy(gol_ctx *d, gol_ctx *c) {
     if (d->rows != c->rows || d->cols != c->cols)
         return fail(d, GOL_EINVAL, "gol_copy needs boards of one size (%lld x %lld <- %lld x %lld)", (long long)d->rows,
                     (long long)d->cols, (long long)c->rows, (long long)c->cols);
-    if (d->transport == GOL_XPORT_RCCL) {
-        const Slab &s = d->slabs[0];
-        return gol_copy_window(d, s.row0, 0, c, s.row0, 0, s.H, d->cols, GOL_COPY_REPLACE);
-    }
-    return gol_copy_window(d, 0, 0, c, 0, 0, d->rows, d->cols, GOL_COPY_REPLACE);
+    const auto [row0, nrows] = own_rows(d);
+    return gol_copy_window(d, row0, 0, c, row0, 0, nrows, d->cols, GOL_COPY_REPLACE);
 }
 
 int64_t gol_text_bytes(int64_t nrows, int64_t ncols) {
@@ -2705,7 +2653,7 @@ int gol_popcount(gol_ctx *c, int64_t *live) {
         unsigned long long v = 0, ghosts = 0;
         HIPCHK(c, hipMemcpyAsync(&v, s.d_count, sizeof v, hipMemcpyDeviceToHost, s.comp));
         if (c->torus) {   // the row popcount took the ghost margins (copies of real cells) along
-            const int gw = c->layout == GOL_LAYOUT_BIT ? c->gw : 0;
+            const int gw = group_width(c);
             HIPCHK(c, hipMemsetAsync(s.d_count, 0, sizeof(unsigned long long), s.comp));
             HIPCHK(c, launch_popcount_cols(s.buf[c->cur], c->pitch_bytes, c->hk, c->hk + s.H, 0, c->xoff, s.d_count,
                                            gw, s.comp));
