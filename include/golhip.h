@@ -398,6 +398,56 @@ int gol_parse_text(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int6
                    int64_t len);
 int gol_read_text(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int fd);
 
+/* RLE pattern text — the run-length format of Life pattern collections:
+ *     x = <ncols>, y = <nrows>, rule = B<digits>/S<digits>\n
+ *     24bo$22bobo$...!\n
+ * A token is an optional count n >= 2 and a tag: b (dead run), o (live run),
+ * $ (end of row), ! (end of pattern).  WRITING is canonical ("RLE
+ * pattern files"): the rule is the context's (gol_get_rule), a row's runs end at
+ * its last live cell, empty rows fold into the next `$` count, trailing empty
+ * rows are left to `y`; with L = 70 / (1 + D), D the decimal digits of
+ * max(nrows, ncols, 1), a '\n' follows every L-th token and `!`, so no line
+ * exceeds 70 characters.  The text is encoded on the device from the window's
+ * logical cells (what gol_download_window returns), in blocks of rows whose worst
+ * case fits GOL_OPT_TEXT_BLOCK_BYTES; only the text crosses PCIe.  Every row of
+ * the window must be held by this context, as for snapshot text; GOL_ESTATE while
+ * the clock probe runs.  An empty window (nrows = 0 or ncols = 0) is its header
+ * and "!\n".
+ *   gol_rle_header  host only, no context: the header line of an RLE text (after any
+ *                   '#' lines).  *body = offset of the first body byte.  *has_rule = 0
+ *                   and B3/S23 in the masks when the header names no rule.  Out
+ *                   pointers may be NULL.  Malformed: GOL_EINVAL.
+ *   gol_rle_bytes   bytes of the window's RLE, header included (row pass + row scan
+ *                   only; synchronises)
+ *   gol_format_rle  text → caller memory; cap too small: GOL_EINVAL, *len = bytes
+ *                   needed, contents of out unspecified
+ *   gol_write_rle   text → file descriptor (write(2), sequential)
+ * READING accepts more than writing produces: leading '#' lines, free spacing in
+ * the header (`x=3,y=3`), an optional `rule = ...` in any notation gol_parse_rule
+ * reads, white space (space, tab, \r, \n) between tokens, anything after `!`.
+ *   gol_parse_rle   header + body from memory; the pattern's top-left cell goes to
+ *                   (row0, col0); x, y (may be NULL) = its box
+ *   gol_read_rle    the same from a file descriptor (read(2), in chunks)
+ * The x × y box at (row0, col0) is REPLACED, cells outside it do not change; a box
+ * that leaves the grid, or rows that are not all held, is GOL_EINVAL before anything
+ * is written; x = 0 or y = 0 reads as GOL_OK and writes nothing.  The header's rule
+ * is NOT set (gol_rle_header + gol_set_rule is the caller's decision).  Malformed
+ * text is GOL_EINVAL with the byte offset in gol_last_error: a rule gol_parse_rule
+ * refuses, any byte that is no count, tag or white space (the multi-state tags `.`
+ * and A..X among them), white space between a count and its tag, a count of 0 or
+ * above 2^31, a run or row that leaves the box, the end of input before `!`; the
+ * box may then be partly written.  The generation, the rule, the options and the
+ * schedule trial stay untouched by all six calls. */
+int gol_rle_header(const char *text, int64_t len, int64_t *x, int64_t *y,
+                   uint32_t *birth, uint32_t *survive, int *has_rule, int64_t *body);
+int gol_rle_bytes(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int64_t *bytes);
+int gol_format_rle(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols,
+                   char *out, int64_t cap, int64_t *len);
+int gol_write_rle(gol_ctx *ctx, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int fd);
+int gol_parse_rle(gol_ctx *ctx, int64_t row0, int64_t col0, const char *text, int64_t len,
+                  int64_t *x, int64_t *y);
+int gol_read_rle(gol_ctx *ctx, int64_t row0, int64_t col0, int fd, int64_t *x, int64_t *y);
+
 /* Live cells held by this context (all its slabs). */
 int gol_popcount(gol_ctx *ctx, int64_t *live);
 

@@ -45,7 +45,7 @@
 //                           iteration I (part files NAME_I_<p>.gol, read back
 //                           on the device); rows/cols/gap/iters default to the
 //                           main file's; new snapshots continue under NAME
-//   --format gol|pbm        the snapshot parts' format (default gol: the reference's text).
+//   --format gol|pbm|rle    the snapshot parts' format (default gol: the reference's text).
 //                           pbm: part files `<name>_<iter>_<part>.pbm`, binary PBM —
 //                           "P4\n# gol <firstRow> <lastRow> <firstCol> <lastCol>\n<ncols> <nrows>\n"
 //                           (the comment carries the four numbers of the .gol header
@@ -53,7 +53,18 @@
 //                           first, 1 = live, packed on the device
 //                           (gol_download_bits_window) — a sixteenth of the text's
 //                           bytes, and any image tool opens it.  With --resume the
-//                           parts NAME_I_<p>.pbm are read back (gol_upload_bits_window)
+//                           parts NAME_I_<p>.pbm are read back (gol_upload_bits_window).
+//                           rle: part files `<name>_<iter>_<part>.rle`, each the RLE pattern
+//                           (gol_write_rle, encoded on the device) of the rows it holds,
+//                           behind a `#CXRLE Pos=<col>,<row>` line with the part's origin,
+//                           which RLE readers take for a comment; with --resume the parts
+//                           NAME_I_<p>.rle are read back (gol_read_rle) at that origin
+//   --pattern FILE[@row,col]  load the RLE pattern FILE onto the starting board (after the
+//                           mode's init or --soup; --soup 0 gives an empty board), its
+//                           top-left cell at (row, col), default (0, 0); its x × y box is
+//                           replaced.  Repeatable, loaded in order.  Without --rule, the
+//                           rule the first pattern's header names is set (gol_rle_header).
+//                           Under --rccl a pattern's rows must lie within one rank's slab
 //   --rccl                  the N row slabs as N RCCL ranks of ONE process: one
 //                           rank context (gol_create_rank) and one communicator
 //                           per device, each driven by a host thread, halo rows
@@ -219,6 +230,64 @@ void read_part_pbm(gol_ctx *ctx, const std::string &path) {
     fclose(f);
 }
 
+// --format rle: the part as an RLE pattern of its own rows, encoded on the device; the leading
+// `#CXRLE Pos=<col>,<row>` line (a comment to RLE readers) carries the part's origin.
+void write_part_rle(gol_ctx *ctx, const std::string &name, int iter, int part, long first_row, long, long first_col,
+                    long, int64_t row0, int64_t nrows, int64_t ncols) {
+    std::string path = name + "_" + std::to_string(iter) + "_" + std::to_string(part) + ".rle";
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) die("cannot create part .rle file");
+    fprintf(f, "#CXRLE Pos=%ld,%ld\n", first_col, first_row);
+    fflush(f);
+    check(ctx, gol_write_rle(ctx, row0, 0, nrows, ncols, fileno(f)), "gol_write_rle");
+    if (fclose(f) != 0) die(("cannot write " + path).c_str());
+}
+
+// Snapshot resume from an .rle part: the origin is the `#CXRLE Pos=` line's, the box the header's.
+void read_part_rle(gol_ctx *ctx, const std::string &path) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) die(("cannot open " + path).c_str());
+    long c0 = 0, r0 = 0;
+    if (fscanf(f, "#CXRLE Pos=%ld,%ld", &c0, &r0) != 2 || fgetc(f) != '\n' || r0 < 0 || c0 < 0)
+        die(("bad header in " + path).c_str());
+    fclose(f);
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) die(("cannot open " + path).c_str());
+    check(ctx, gol_read_rle(ctx, r0, c0, fd, nullptr, nullptr), path.c_str());
+    close(fd);
+}
+
+// --pattern FILE[@row,col]: the file's bytes, where it goes, what its header says
+struct Pattern {
+    std::string path, text;
+    int64_t row = 0, col = 0, x = 0, y = 0;
+    uint32_t birth = 0, survive = 0;
+    int has_rule = 0;
+};
+Pattern load_pattern(const std::string &arg) {
+    Pattern p;
+    p.path = arg;
+    const size_t at = arg.rfind('@');
+    if (at != std::string::npos) {
+        long long r = 0, c = 0;
+        int used = 0;
+        if (sscanf(arg.c_str() + at + 1, "%lld,%lld%n", &r, &c, &used) != 2 || arg[at + 1 + used] || r < 0 || c < 0)
+            die("--pattern must be FILE or FILE@row,col");
+        p.path = arg.substr(0, at);
+        p.row = r;
+        p.col = c;
+    }
+    FILE *f = fopen(p.path.c_str(), "rb");
+    if (!f) die(("--pattern: cannot open " + p.path).c_str());
+    char buf[1 << 16];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) p.text.append(buf, n);
+    fclose(f);
+    if (gol_rle_header(p.text.data(), (int64_t)p.text.size(), &p.x, &p.y, &p.birth, &p.survive, &p.has_rule, nullptr) !=
+        GOL_OK)
+        die(("--pattern: no RLE header in " + p.path).c_str());
+    return p;
+}
+
 struct Opts {
     std::string mode = "mpi", layout = "", format = "gol";
     int procs = 1, gpus = 1, k = 1, save = -1;
@@ -232,6 +301,7 @@ struct Opts {
     std::string rule_kernel = "auto";   // --rule-kernel: auto | generic
     bool digest = false;  // --digest: print the board's digest at every snapshot point and at the end
     int64_t tile_rows = 0, tile_cols = 0;   // --density T[xU] (0: no map)
+    std::vector<std::string> patterns;      // --pattern FILE[@row,col], in order
 };
 
 // One rank of --rccl: its context and what it reports.
@@ -304,6 +374,7 @@ int main(int argc, char **argv) {
         else if (a == "--rccl-lib") o.rccl_lib = next();
         else if (a == "--same-device") o.same_device = true;
         else if (a == "--digest") o.digest = true;
+        else if (a == "--pattern") o.patterns.push_back(next());
         else if (a == "--density") {
             const char *v = next();
             char *end = nullptr;
@@ -321,8 +392,10 @@ int main(int argc, char **argv) {
         }
         else pos.push_back(argv[i]);
     }
-    if (o.format != "gol" && o.format != "pbm") die("--format must be gol or pbm");
-    const bool pbm = o.format == "pbm";
+    if (o.format != "gol" && o.format != "pbm" && o.format != "rle") die("--format must be gol, pbm or rle");
+    const bool pbm = o.format == "pbm", rle = o.format == "rle";
+    std::vector<Pattern> patterns;
+    for (const std::string &a : o.patterns) patterns.push_back(load_pattern(a));
     uint64_t soup_threshold = 0;
     if (!o.soup.empty()) {
         char *end = nullptr;
@@ -396,6 +469,13 @@ int main(int argc, char **argv) {
                 "which knows B3/S23 only)");
         if (layout != GOL_LAYOUT_BIT) die("--rule needs --layout bit (the byte layout computes B3/S23 only)");
     }
+    // --pattern without --rule: the rule the first pattern's header names
+    bool pattern_rule = false;
+    if (o.rule.empty() && !patterns.empty() && patterns[0].has_rule) {
+        birth = patterns[0].birth;
+        survive = patterns[0].survive;
+        pattern_rule = true;
+    }
     if (o.seed >= 0) seed = (uint32_t)o.seed;
     if (gap <= 0 && save) die("iteration_gap must be positive when saving");
 
@@ -428,7 +508,7 @@ int main(int argc, char **argv) {
     if (o.rccl) check(nullptr, gol_get_unique_id(uid), "gol_get_unique_id");
     // part p of a snapshot: the rows of slab p, written by the context holding them
     auto write_snap = [&](gol_ctx *ctx, int iter, int p) {
-        const auto part = pbm ? write_part_pbm : write_part;
+        const auto part = rle ? write_part_rle : pbm ? write_part_pbm : write_part;
         if (o.mode == "serial" && parts == 1)   // main_serial.cpp:164-167: "0 n" / "0 n"
             part(ctx, name, iter, p, 0, rows, 0, cols, 0, rows, cols);
         else   // main.cpp:255-258: inclusive ranges (gol_visualization.py:33 slices [min, max+1])
@@ -443,7 +523,8 @@ int main(int argc, char **argv) {
         else
             check(nullptr, gol_create(&ctx, rows, cols, o.gpus, layout, boundary, m, o.k), "gol_create");
         rk[i].ctx = ctx;
-        if (!o.rule.empty()) check(ctx, gol_set_rule(ctx, birth, survive), "gol_set_rule");   // (-k >= 8: its message)
+        if (!o.rule.empty() || pattern_rule)
+            check(ctx, gol_set_rule(ctx, birth, survive), "gol_set_rule");   // (-k >= 8: its message)
         if (o.rule_kernel == "generic") check(ctx, gol_set_option(ctx, GOL_OPT_RULE_COMPILED, 0), "GOL_OPT_RULE_COMPILED");
         // launches are counted on the host (gol_kernel_time without GOL_OPT_KERNEL_TIMING): no event pair
         // per launch inside the timed region
@@ -454,8 +535,21 @@ int main(int argc, char **argv) {
         } else {
             for (int p = 0; p < m_parts; ++p)
                 if (!o.rccl || p == i)
-                    (pbm ? read_part_pbm : read_part)(ctx, o.resume + "_" + std::to_string(from) + "_" +
-                                                               std::to_string(p) + (pbm ? ".pbm" : ".gol"));
+                    (rle ? read_part_rle : pbm ? read_part_pbm : read_part)(
+                        ctx, o.resume + "_" + std::to_string(from) + "_" + std::to_string(p) +
+                                 (rle ? ".rle" : pbm ? ".pbm" : ".gol"));
+        }
+        // --pattern: onto the starting board, in order (a rank loads the patterns whose rows it holds)
+        for (size_t j = 0; o.resume.empty() && j < patterns.size(); ++j) {
+            const Pattern &pt = patterns[j];
+            if (o.rccl) {
+                const bool above = pt.row + pt.y <= row0[i], below = pt.row >= row0[i] + nrow[i];
+                if (above || below) continue;
+                if (pt.row < row0[i] || pt.row + pt.y > row0[i] + nrow[i])
+                    die(("--pattern: the rows of " + pt.path + " straddle two ranks' slabs").c_str());
+            }
+            check(ctx, gol_parse_rle(ctx, pt.row, pt.col, pt.text.data(), (int64_t)pt.text.size(), nullptr, nullptr),
+                  pt.path.c_str());
         }
         // main_serial.cpp:171 writes generation 0; main.cpp:285 has that write commented out, which
         // leaves gol_visualization.py without its iteration-0 files, so every saving mode writes it.

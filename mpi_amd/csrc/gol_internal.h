@@ -230,4 +230,21 @@ hipError_t launch_copy_cells(const void *src, int64_t src_pitch_bytes, int64_t s
                              int64_t dst_pitch_bytes, int64_t dr0, int64_t dpc0, int dst_gw, int64_t nrows,
                              int64_t ncols, int64_t active_cols, int op, hipStream_t s);
 
+// ---- gol_format_rle / gol_write_rle / gol_rle_bytes: RLE text of packed rows (gol_rle.h, gol_rle.hip) ----
+// `packed` holds nrows rows of pitch_words u32 as launch_get_bits leaves them (pad bits 0), ncols >= 1
+// cells each.  rows: tokens and token bytes (no newlines) per row.  scan (one workgroup): row r of the
+// block is window row row_base + r; last_row = the last non-empty window row before the block (-1: none),
+// tok0 = the tokens before it, L = tokens per line; per row the `$` count (0: none), the index of its
+// first token and its byte offset in the block's text; *rec = the block's bytes, the token index and the
+// last non-empty row behind it.  write: the tokens at their offsets (rec->bytes bytes of `text`).
+struct RleRecord;
+hipError_t launch_rle_rows(const uint32_t *packed, int64_t pitch_words, int64_t nrows, int64_t ncols, uint32_t *ntok,
+                           uint32_t *nraw, hipStream_t s);
+hipError_t launch_rle_scan(const uint32_t *ntok, const uint32_t *nraw, int64_t nrows, int64_t row_base,
+                           int64_t last_row, int64_t tok0, int L, uint32_t *dcount, int64_t *tix, int64_t *off,
+                           RleRecord *rec, hipStream_t s);
+hipError_t launch_rle_write(const uint32_t *packed, int64_t pitch_words, int64_t nrows, int64_t ncols,
+                            const uint32_t *ntok, const uint32_t *dcount, const int64_t *tix, const int64_t *off, int L,
+                            char *text, hipStream_t s);
+
 } // namespace gol

@@ -34,6 +34,7 @@
 #include "glibc_jump.h"
 #include "gol_fill.h"
 #include "gol_internal.h"
+#include "gol_rle.h"
 
 using namespace gol;
 
@@ -1997,6 +1998,285 @@ int text_io(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols
     return GOL_OK;
 }
 
+// ------------------------------------------------------------------ RLE pattern text
+// gol_rle.h holds the format.  Writing follows text_io: per slab piece, blocks of rows sized
+// so that the worst case of a block (rle_rows_bound) fits GOL_OPT_TEXT_BLOCK_BYTES, per-call
+// staging, the slab's comm stream, two pinned text buffers.  A block takes two enqueues:
+//   A  clear the packed staging, launch_get_bits per column run, row pass, row scan (carry-in:
+//      the last non-empty row and the token index, which the host carries from block to block
+//      and from piece to piece), the scan's record to the host;
+//   B  once the record is read: the write pass and a copy of exactly rec->bytes bytes.
+// The host writes block i - 1 out while B(i) and A(i + 1) run.  Counting (gol_rle_bytes, a
+// memory sink that overflowed) stops after A.
+struct RleBuffers {
+    char *pinned[2] = {nullptr, nullptr};   // text blocks (write) / packed row blocks (read)
+    RleRecord *rec = nullptr;               // pinned
+    uint32_t *dpacked = nullptr, *dcnt = nullptr;
+    int64_t *dpos = nullptr;
+    RleRecord *drec = nullptr;
+    char *dtext = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr}, evrec = nullptr;
+    ~RleBuffers() {
+        for (int i = 0; i < 2; ++i) {
+            if (pinned[i]) (void)hipHostFree(pinned[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+        if (evrec) (void)hipEventDestroy(evrec);
+        if (rec) (void)hipHostFree(rec);
+        if (dpacked) (void)hipFree(dpacked);
+        if (dcnt) (void)hipFree(dcnt);
+        if (dpos) (void)hipFree(dpos);
+        if (drec) (void)hipFree(drec);
+        if (dtext) (void)hipFree(dtext);
+    }
+};
+
+int rle_header_text(const gol_ctx *c, int64_t nrows, int64_t ncols, char *out, size_t cap) {
+    char b[10], s[10];
+    int nb = 0, ns = 0;
+    for (int i = 0; i <= 8; ++i) {
+        if (c->rule.birth >> i & 1u) b[nb++] = (char)('0' + i);
+        if (c->rule.survive >> i & 1u) s[ns++] = (char)('0' + i);
+    }
+    b[nb] = s[ns] = '\0';
+    return snprintf(out, cap, "x = %lld, y = %lld, rule = B%s/S%s\n", (long long)ncols, (long long)nrows, b, s);
+}
+
+// h = null: count only.  cap: what a memory sink holds; bytes beyond it are counted, not produced.
+// *total = the bytes of the whole text; *over = the sink was too small.
+int rle_out(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, TextHost *h, int64_t cap,
+            int64_t *total, bool *over) {
+    if (int rc = check_window(c, row0, col0, nrows, ncols)) return rc;
+    int64_t produced = 0;
+    bool full = false;
+    auto room = [&](int64_t n) {   // account n bytes; are they to be produced?
+        if (h && !full && produced + n > cap) full = true;
+        produced += n;
+        return h && !full;
+    };
+    char head[96];
+    const int hn = rle_header_text(c, nrows, ncols, head, sizeof head);
+    if (room(hn))
+        if (int rc = host_put(c, *h, head, hn)) return rc;
+    const int L = rle_line_tokens(nrows, ncols), D = rle_digits(std::max<int64_t>(1, std::max(nrows, ncols)));
+    int64_t last_row = -1, tok = 0;   // the carries
+    if (nrows > 0 && ncols > 0) {
+        if (rows_held(c, row0, nrows) != nrows)
+            return fail(c, GOL_EINVAL, "RLE window rows are not all held by this context");
+        if (c->clk_running) return fail(c, GOL_ESTATE, "RLE text while the clock probe runs");   // (allocates: text_io)
+        if (int rc = sync_all(c, nullptr)) return rc;
+        const int64_t br = std::max<int64_t>(1, c->text_block_bytes / rle_rows_bound(1, ncols, L, D));
+        const int64_t pw = bits_pitch(ncols) / 4;
+        for (const Piece &p : window_pieces(c, row0, nrows)) {
+            Slab &s = *p.s;
+            HIPCHK(c, hipSetDevice(s.device));
+            const int64_t pr = p.r1 - p.r0, nb = (pr + br - 1) / br, bmax = std::min(br, pr);
+            const int64_t tcap = rle_rows_bound(bmax, ncols, L, D);
+            RleBuffers t;
+            HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&t.rec), sizeof(RleRecord), hipHostMallocDefault));
+            HIPCHK(c, hipEventCreateWithFlags(&t.evrec, hipEventDisableTiming));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&t.dpacked), (size_t)(bmax * pw * 4)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&t.dcnt), (size_t)(3 * bmax) * sizeof(uint32_t)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&t.dpos), (size_t)(2 * bmax) * sizeof(int64_t)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&t.drec), sizeof(RleRecord)));
+            if (h && !full) {
+                HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&t.dtext), (size_t)round_up(tcap, 256)));
+                for (int i = 0; i < 2; ++i) {
+                    HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&t.pinned[i]), (size_t)tcap, hipHostMallocDefault));
+                    HIPCHK(c, hipEventCreateWithFlags(&t.ev[i], hipEventDisableTiming));
+                }
+            }
+            const uint8_t *cur = static_cast<const uint8_t *>(s.buf[c->cur]);
+            auto rows_of = [&](int64_t i) { return std::min(br, pr - i * br); };
+            auto pass_a = [&](int64_t i) -> int {
+                const int64_t nr = rows_of(i), srow = p.srow + i * br;
+                tr_op(c, TR_READ, s.comm, nullptr, s.index, c->cur, srow, srow + nr);
+                HIPCHK(c, hipMemsetAsync(t.dpacked, 0, (size_t)(nr * pw * 4), s.comm));
+                int rc = for_col_runs(c, col0, ncols, [&](int64_t lc, int64_t pc, int64_t n) -> int {
+                    HIPCHK(c, launch_get_bits(cur, c->pitch_bytes, srow, srow + nr, pc, lc - col0, n, t.dpacked, pw,
+                                              group_width(c), s.comm));
+                    return GOL_OK;
+                });
+                if (rc) return rc;
+                HIPCHK(c, launch_rle_rows(t.dpacked, pw, nr, ncols, t.dcnt, t.dcnt + bmax, s.comm));
+                HIPCHK(c, launch_rle_scan(t.dcnt, t.dcnt + bmax, nr, (p.r0 - row0) + i * br, last_row, tok, L,
+                                          t.dcnt + 2 * bmax, t.dpos, t.dpos + bmax, t.drec, s.comm));
+                HIPCHK(c, hipMemcpyAsync(t.rec, t.drec, sizeof(RleRecord), hipMemcpyDeviceToHost, s.comm));
+                HIPCHK(c, tr_record(c, t.evrec, s.comm));
+                return GOL_OK;
+            };
+            auto pass_b = [&](int64_t i, int64_t bytes) -> int {
+                HIPCHK(c, launch_rle_write(t.dpacked, pw, rows_of(i), ncols, t.dcnt, t.dcnt + 2 * bmax, t.dpos,
+                                           t.dpos + bmax, L, t.dtext, s.comm));
+                HIPCHK(c, hipMemcpyAsync(t.pinned[i & 1], t.dtext, (size_t)bytes, hipMemcpyDeviceToHost, s.comm));
+                HIPCHK(c, tr_record(c, t.ev[i & 1], s.comm));
+                return GOL_OK;
+            };
+            int64_t held[2] = {0, 0};   // bytes of the block waiting in pinned[k] for the host
+            auto drain = [&](int64_t i) -> int {
+                if (i < 0 || !held[i & 1]) return GOL_OK;
+                HIPCHK(c, tr_esync(c, t.ev[i & 1]));
+                const int64_t n = held[i & 1];
+                held[i & 1] = 0;
+                return host_put(c, *h, t.pinned[i & 1], n);
+            };
+            auto run = [&]() -> int {
+                if (int rc = pass_a(0)) return rc;
+                for (int64_t i = 0; i < nb; ++i) {
+                    HIPCHK(c, tr_esync(c, t.evrec));
+                    const RleRecord rec = *t.rec;
+                    if (rec.bytes < 0 || rec.bytes > rle_rows_bound(rows_of(i), ncols, L, D) || rec.tokens < tok)
+                        return fail(c, GOL_EHIP, "RLE row scan: a record outside its bound (%lld bytes of %lld)",
+                                    (long long)rec.bytes, (long long)rle_rows_bound(rows_of(i), ncols, L, D));
+                    last_row = rec.last_row;
+                    tok = rec.tokens;
+                    if (room(rec.bytes) && rec.bytes && t.dtext) {
+                        if (int rc = pass_b(i, rec.bytes)) return rc;
+                        held[i & 1] = rec.bytes;
+                    }
+                    if (i + 1 < nb)
+                        if (int rc = pass_a(i + 1)) return rc;
+                    if (int rc = drain(i - 1)) return rc;
+                }
+                return drain(nb - 1);
+            };
+            const int rc = run();
+            HIPCHK(c, tr_ssync(c, s.comm));   // nothing in flight when the staging goes
+            if (rc) return rc;
+        }
+    }
+    if (room(2))
+        if (int rc = host_put(c, *h, "!\n", 2)) return rc;
+    *total = produced;
+    if (over) *over = full;
+    return GOL_OK;
+}
+
+// Reading: header, then the body through RleParser into blocks of packed rows (pinned, two
+// alternating), each uploaded and merged by launch_put_bits per column run, as
+// gol_upload_bits_window's; a block without a live cell is cleared by the constant fill instead.
+// text = null: from fd, in chunks.
+int rle_in(gol_ctx *c, int64_t row0, int64_t col0, const char *text, int64_t len, int fd, int64_t *xo, int64_t *yo) {
+    std::string chunk;   // fd: the bytes being parsed
+    const char *cp = nullptr;
+    int64_t cn = 0;
+    bool eof = text != nullptr;
+    auto more = [&](std::string &into, size_t at) -> int {
+        into.resize(at + (1 << 16));
+        ssize_t r;
+        do r = read(fd, &into[at], 1 << 16);
+        while (r < 0 && errno == EINTR);
+        if (r < 0) return fail(c, GOL_EINVAL, "read(fd %d): %s", fd, strerror(errno));
+        into.resize(at + (size_t)r);
+        if (r == 0) eof = true;
+        return GOL_OK;
+    };
+    int64_t x = 0, y = 0, ra = 0, rl = 0, body = 0;
+    int hs;
+    if (text) {
+        hs = rle_header_scan(text, len, true, &x, &y, &ra, &rl, &body);
+    } else {
+        do {
+            if (int rc = more(chunk, chunk.size())) return rc;
+            hs = rle_header_scan(chunk.data(), (int64_t)chunk.size(), eof, &x, &y, &ra, &rl, &body);
+        } while (hs == 1);
+    }
+    const char *all = text ? text : chunk.data();
+    if (hs) return fail(c, GOL_EINVAL, "malformed RLE header at byte %lld", (long long)body);
+    if (rl) {
+        uint32_t b = 0, sv = 0;
+        if (gol_parse_rule(std::string(all + ra, (size_t)rl).c_str(), &b, &sv) != GOL_OK)
+            return fail(c, GOL_EINVAL, "RLE header: rule text refused at byte %lld", (long long)ra);
+    }
+    if (xo) *xo = x;
+    if (yo) *yo = y;
+    if (x == 0 || y == 0) return GOL_OK;
+    if (check_window(c, row0, col0, y, x))
+        return fail(c, GOL_EINVAL, "the %lld x %lld box of the RLE text leaves the grid at (%lld, %lld)", (long long)y,
+                    (long long)x, (long long)row0, (long long)col0);
+    if (rows_held(c, row0, y) != y) return fail(c, GOL_EINVAL, "RLE box rows are not all held by this context");
+    if (c->clk_running) return fail(c, GOL_ESTATE, "RLE text while the clock probe runs");
+    if (int rc = sync_all(c, nullptr)) return rc;
+    if (!text) chunk.erase(0, (size_t)body);
+    cp = text ? text + body : chunk.data();
+    cn = text ? len - body : (int64_t)chunk.size();
+    RleParser ps(x, y, body);
+    auto bad = [&]() {
+        return fail(c, GOL_EINVAL, "malformed RLE text at byte %lld: %s", (long long)ps.error_offset(), ps.reason());
+    };
+    // feed until the parser wants the next block (0), has read `!` (1) or fails (an error code)
+    auto pump = [&]() -> int {
+        for (;;) {
+            if (ps.done()) return 1;
+            if (cn == 0) {
+                if (!eof) {
+                    if (int rc = more(chunk, 0)) return rc;
+                    cp = chunk.data();
+                    cn = (int64_t)chunk.size();
+                    continue;
+                }
+                ps.finish();
+                return bad();
+            }
+            int64_t used = 0;
+            const RleParser::Status st = ps.feed(cp, cn, &used);
+            cp += used;
+            cn -= used;
+            if (st == RleParser::kError) return bad();
+            if (st == RleParser::kBlock) return 0;
+        }
+    };
+    const int64_t pitch = bits_pitch(x), br = std::max<int64_t>(1, c->text_block_bytes / pitch);
+    for (const Piece &p : window_pieces(c, row0, y)) {
+        Slab &s = *p.s;
+        HIPCHK(c, hipSetDevice(s.device));
+        const int64_t pr = p.r1 - p.r0, nb = (pr + br - 1) / br, bmax = std::min(br, pr);
+        RleBuffers t;
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&t.pinned[i]), (size_t)(bmax * pitch), hipHostMallocDefault));
+            HIPCHK(c, hipEventCreateWithFlags(&t.ev[i], hipEventDisableTiming));
+        }
+        HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&t.dpacked), (size_t)(bmax * pitch)));
+        uint8_t *cur = static_cast<uint8_t *>(s.buf[c->cur]);
+        auto run = [&]() -> int {
+            for (int64_t i = 0; i < nb; ++i) {
+                const int64_t a = p.r0 + i * br, nr = std::min(br, p.r1 - a), srow = p.srow + i * br;
+                if (i >= 2) HIPCHK(c, tr_esync(c, t.ev[i & 1]));   // block i - 2's copy has left the buffer
+                uint8_t *pin = reinterpret_cast<uint8_t *>(t.pinned[i & 1]);
+                memset(pin, 0, (size_t)(nr * pitch));
+                ps.set_block(pin, pitch, a - row0, nr);
+                const int st = pump();
+                if (st < 0) return st;
+                tr_op(c, TR_WRITE, s.comm, nullptr, s.index, c->cur, srow, srow + nr);
+                if (ps.live())
+                    HIPCHK(c, hipMemcpyAsync(t.dpacked, pin, (size_t)(nr * pitch), hipMemcpyHostToDevice, s.comm));
+                int rc = for_col_runs(c, col0, x, [&](int64_t lc, int64_t pc, int64_t n) -> int {
+                    if (ps.live())
+                        HIPCHK(c, launch_put_bits(cur, c->pitch_bytes, srow, srow + nr, pc, lc - col0, n, c->active_cols,
+                                                  t.dpacked, pitch / 4, group_width(c), s.comm));
+                    else   // all dead: the constant fill, nothing crosses PCIe
+                        HIPCHK(c, launch_fill_random(cur, c->pitch_bytes, srow, srow + nr, a, pc, lc, n, c->active_cols,
+                                                     0, 0, group_width(c), s.comm));
+                    return GOL_OK;
+                });
+                if (rc) return rc;
+                if (int rc2 = wrap_rows(c, s, c->cur, srow, srow + nr, s.comm)) return rc2;
+                HIPCHK(c, tr_record(c, t.ev[i & 1], s.comm));
+            }
+            return GOL_OK;
+        };
+        int rc = run();
+        HIPCHK(c, tr_ssync(c, s.comm));
+        if (!rc) rc = enforce_inactive(c, s, c->cur);
+        HIPCHK(c, tr_ssync(c, s.comp));
+        if (rc) return rc;
+    }
+    // what follows the last block: `$`, `!`, white space (a live run would lie outside the box)
+    ps.set_block(nullptr, 0, y, 0);
+    const int st = pump();
+    return st < 0 ? st : GOL_OK;
+}
+
 // Hardware queues a process gets per device: GPU_MAX_HW_QUEUES, HIP's default 4.
 int hw_queue_budget() {
     const char *v = getenv("GPU_MAX_HW_QUEUES");
@@ -2615,6 +2895,57 @@ int gol_read_text(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t
     TextHost h;
     h.fd = fd;
     return text_io(c, row0, col0, nrows, ncols, h, true);
+}
+
+int gol_rle_header(const char *text, int64_t len, int64_t *x, int64_t *y, uint32_t *birth, uint32_t *survive,
+                   int *has_rule, int64_t *body) {
+    if (!text || len < 0) return GOL_EINVAL;
+    int64_t hx = 0, hy = 0, ra = 0, rl = 0, hb = 0;
+    if (rle_header_scan(text, len, true, &hx, &hy, &ra, &rl, &hb)) return GOL_EINVAL;
+    uint32_t b = kLifeBirth, s = kLifeSurvive;
+    if (rl && gol_parse_rule(std::string(text + ra, (size_t)rl).c_str(), &b, &s) != GOL_OK) return GOL_EINVAL;
+    if (x) *x = hx;
+    if (y) *y = hy;
+    if (birth) *birth = b;
+    if (survive) *survive = s;
+    if (has_rule) *has_rule = rl != 0;
+    if (body) *body = hb;
+    return GOL_OK;
+}
+
+int gol_rle_bytes(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int64_t *bytes) {
+    if (!c || !bytes) return GOL_EINVAL;
+    return rle_out(c, row0, col0, nrows, ncols, nullptr, 0, bytes, nullptr);
+}
+
+int gol_format_rle(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, char *out, int64_t cap,
+                   int64_t *len) {
+    if (!c || !len || cap < 0 || (!out && cap > 0)) return GOL_EINVAL;
+    TextHost h;
+    h.out = out;
+    bool over = false;
+    if (int rc = rle_out(c, row0, col0, nrows, ncols, out ? &h : nullptr, cap, len, &over)) return rc;
+    if (over || (!out && *len > 0))
+        return fail(c, GOL_EINVAL, "the RLE text needs %lld bytes, the buffer holds %lld", (long long)*len, (long long)cap);
+    return GOL_OK;
+}
+
+int gol_write_rle(gol_ctx *c, int64_t row0, int64_t col0, int64_t nrows, int64_t ncols, int fd) {
+    if (!c || fd < 0) return GOL_EINVAL;
+    TextHost h;
+    h.fd = fd;
+    int64_t total = 0;
+    return rle_out(c, row0, col0, nrows, ncols, &h, INT64_MAX, &total, nullptr);
+}
+
+int gol_parse_rle(gol_ctx *c, int64_t row0, int64_t col0, const char *text, int64_t len, int64_t *x, int64_t *y) {
+    if (!c || !text || len < 0) return GOL_EINVAL;
+    return rle_in(c, row0, col0, text, len, -1, x, y);
+}
+
+int gol_read_rle(gol_ctx *c, int64_t row0, int64_t col0, int fd, int64_t *x, int64_t *y) {
+    if (!c || fd < 0) return GOL_EINVAL;
+    return rle_in(c, row0, col0, nullptr, 0, fd, x, y);
 }
 
 int gol_step(gol_ctx *c, int64_t generations) {

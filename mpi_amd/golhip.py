@@ -57,6 +57,7 @@ EXPORTS = [
     "gol_fill_threshold", "gol_fill_random", "gol_fill_random_window",
     "gol_copy_window", "gol_copy",
     "gol_compiled_rule", "gol_rule_path",
+    "gol_rle_header", "gol_rle_bytes", "gol_format_rle", "gol_write_rle", "gol_parse_rle", "gol_read_rle",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -139,6 +140,13 @@ def load() -> ctypes.CDLL:
         "gol_copy": ([P, P], i32),
         "gol_compiled_rule": ([i32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_char_p)], i32),
         "gol_rule_path": ([P, ctypes.POINTER(i32)], i32),
+        "gol_rle_header": ([ctypes.c_char_p, i64, i64p, i64p, ctypes.POINTER(u32), ctypes.POINTER(u32),
+                            ctypes.POINTER(i32), i64p], i32),
+        "gol_rle_bytes": ([P, i64, i64, i64, i64, i64p], i32),
+        "gol_format_rle": ([P, i64, i64, i64, i64, ctypes.c_char_p, i64, i64p], i32),
+        "gol_write_rle": ([P, i64, i64, i64, i64, i32], i32),
+        "gol_parse_rle": ([P, i64, i64, ctypes.c_char_p, i64, i64p, i64p], i32),
+        "gol_read_rle": ([P, i64, i64, i32, i64p, i64p], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -169,6 +177,20 @@ def parse_rule(text: str) -> tuple[int, int]:
     if rc:
         raise GolError(rc, f"gol_parse_rule: not a B/S rule: {text!r}")
     return b.value, s.value
+
+
+def rle_header(text: bytes | str) -> tuple[int, int, tuple[int, int] | None, int]:
+    """(x, y, rule, body) of an RLE text's header line (behind any '#' lines): the pattern's box,
+    the (birth, survive) masks of its `rule = ...` or None if it names none, and the offset of the
+    first body byte (gol_rle_header).  Host-only."""
+    t = text.encode() if isinstance(text, str) else bytes(text)
+    x, y, body = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    b, s, has = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int()
+    rc = load().gol_rle_header(t, len(t), ctypes.byref(x), ctypes.byref(y), ctypes.byref(b), ctypes.byref(s),
+                               ctypes.byref(has), ctypes.byref(body))
+    if rc:
+        raise GolError(rc, "gol_rle_header: not an RLE header")
+    return x.value, y.value, ((b.value, s.value) if has.value else None), body.value
 
 
 def compiled_rules() -> list[tuple[str, int, int]]:
@@ -631,6 +653,58 @@ class Engine:
         finally:
             os.close(fd)
         return row0, col0, nrows, ncols
+
+    # ------------------------------------------------------------ RLE pattern text
+    def _rle_window(self, window):
+        return (0, 0, self.rows, self.cols) if window is None else tuple(int(v) for v in window)
+
+    def rle_bytes(self, window=None) -> int:
+        """Bytes of format_rle(window), header included: the two counting passes on the device."""
+        n = ctypes.c_int64()
+        self._chk(self.lib.gol_rle_bytes(self._c, *self._rle_window(window), ctypes.byref(n)), "gol_rle_bytes")
+        return n.value
+
+    def format_rle(self, window=None) -> bytes:
+        """The RLE text (header with the rule in force, canonical body) of window = (row0, col0,
+        nrows, ncols), default the whole board, encoded on the device."""
+        w = self._rle_window(window)
+        cap = self.rle_bytes(w)
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        n = ctypes.c_int64()
+        self._chk(self.lib.gol_format_rle(self._c, *w, buf, cap, ctypes.byref(n)), "gol_format_rle")
+        return buf.raw[:n.value]
+
+    def save_rle(self, path: str, window=None):
+        """format_rle streamed to a file."""
+        with open(path, "wb") as f:
+            self._chk(self.lib.gol_write_rle(self._c, *self._rle_window(window), f.fileno()), "gol_write_rle")
+
+    def parse_rle(self, text: bytes | str, at: tuple[int, int] = (0, 0)) -> tuple[int, int]:
+        """Load an RLE text: its x × y box at `at` = (row, col) is replaced.  Returns (x, y).
+        The header's rule is not applied (rle_header + set_rule, or load_rle(set_rule=True))."""
+        t = text.encode() if isinstance(text, str) else bytes(text)
+        x, y = ctypes.c_int64(), ctypes.c_int64()
+        self._chk(self.lib.gol_parse_rle(self._c, at[0], at[1], t, len(t), ctypes.byref(x), ctypes.byref(y)),
+                  "gol_parse_rle")
+        return x.value, y.value
+
+    def load_rle(self, path: str, at: tuple[int, int] = (0, 0), set_rule: bool = False) -> tuple[int, int]:
+        """parse_rle from a file, read in chunks.  set_rule: apply the header's rule (if it names
+        one) before anything is written."""
+        if set_rule:
+            with open(path, "rb") as f:
+                head = f.read(1 << 16)
+            rule = rle_header(head)[2]
+            if rule is not None:
+                self.set_rule(rule)
+        x, y = ctypes.c_int64(), ctypes.c_int64()
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            self._chk(self.lib.gol_read_rle(self._c, at[0], at[1], fd, ctypes.byref(x), ctypes.byref(y)),
+                      "gol_read_rle")
+        finally:
+            os.close(fd)
+        return x.value, y.value
 
     # ------------------------------------------------------------ hot path
     def step(self, generations: int = 1):
